@@ -6,7 +6,10 @@ pq_dim=64, pq_bits=8, n_lists=16384, n_probes=128, batch = 10k queries, k = 10, 
 A "step" is one cuvsIvfPqSearch (k * refine_ratio candidates) + cuvsRefine over one resident batch of 10k queries.
 Index build, ground truth and the CPU baseline are outside the timed region; queries/outputs are resident in HBM.
 
-  python bench.py                      # N=1: headline + the other LUT/score precisions + C1/C2/C4 lines + live PMC passes
+  python bench.py                      # N=1: the headline only (set-up, warm-up, the timed steps, the JSON line)
+  python bench.py --full               # N=1: headline + recall + the other LUT/score precisions + C1/C2/C4 lines + live PMC
+                                       # passes + CPU baseline (the same split for --gpus N and --config c5)
+  python bench.py --dump-outputs DIR   # also writes what the last timed step returned: DIR/<name>.npy (float32 / float64)
   python bench.py --gpus N             # N > 1 with no launcher around it: bench.py starts its own N ranks (one per GPU,
                                        # torch.distributed.run on 127.0.0.1) and fails loudly when the node has fewer than N
                                        # devices. List-sharded index (lists dealt to the ranks by size), every step ends in
@@ -23,6 +26,9 @@ Index build, ground truth and the CPU baseline are outside the timed region; que
 
 Prints ONE JSON line (rank 0):
   value / ms_per_step    the headline variant: fp16 LUT / fp32 scores, the arithmetic of the reference's own bench grid
+With --full the line also holds (each of these is measured or checked outside the timed steps):
+  recall_at_10           recall of the headline's last step against an exact fp64 search of the first --gt-queries queries
+  scan3_equals_lut_scan  the headline's ids and distances equal those of the LUT scan kernels on the first 1000 queries
   config.variants        the same step with the reference-default arithmetic (fp32 LUT / fp32 scores), fp16 / fp16 and
                          the fp8 LUT, each with ms, recall and scan-kernel time
   config.metric_variants the same search on an inner-product and a cosine index of the same rows
@@ -136,6 +142,16 @@ def dist_setup(args):
     return rank, world, dev, dist, shared
 
 
+def finish_ranks(world, dist, comm):
+    """the end of every rank's run"""
+    if world > 1:
+        dist.barrier()  # rank 0 may still be in its CPU leg: nobody tears the communicators down under it
+    if comm is not None:
+        comm.close()
+    if world > 1:
+        dist.destroy_process_group()
+
+
 def ctl_tensor(values, dtype, dev, shared):
     """a small tensor for a control-plane collective: on the device under nccl, on the host under gloo"""
     return torch.tensor(values, dtype=dtype, device="cpu" if shared else dev)
@@ -163,6 +179,29 @@ def emit_json(obj):
         pass
     line = (json.dumps(obj) + "\n").encode()
     os.write(_REAL_STDOUT if _REAL_STDOUT is not None else 1, line)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: the arrays the timed path returned in its last step, as DIR/<name>.npy - ids as float64 (exact below
+    2^53), values as float32. Above 64 MB in all, the same fixed, seeded sample of rows of every array (DIR/sample_rows.npy)."""
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[name] = a.astype(np.float64 if a.dtype.kind in "iu" or a.dtype == np.float64 else np.float32)
+    n = next(iter(host.values())).shape[0]
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = max(1, DUMP_LIMIT_BYTES // (total // n + 8))  # (+ 8 bytes per row: sample_rows)
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        host = {name: a[rows] for name, a in host.items()}
+        host["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    log(f"outputs of the last timed step written to {dirname}: " + ", ".join(f"{k} {list(v.shape)}" for k, v in host.items()))
 
 
 def flush_c_stdio_to_stderr():
@@ -547,7 +586,7 @@ def run_c5(args):
 
     for _ in range(args.warmup):
         step()
-    lib().cuvsAmdProfileEnable(1)
+    lib().cuvsAmdProfileEnable(1 if args.full else 0)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -565,6 +604,24 @@ def run_c5(args):
         t = ctl_tensor([elapsed], torch.float64, dev, shared_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"neighbors": out_i, "distances": out_d})
+    line = {
+        "metric": f"QPS, IVF-PQ {rows}x96 int8 list-sharded, batch={args.batch} per GPU",
+        "value": round(nq_total / (elapsed / args.steps), 1), "unit": "queries/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": f"u8 codes, {args.lut} LUT, {args.acc} score", "data": "synthetic",
+        "config": {"workload": f"C5 IVF-PQ {rows}x96 int8, pq_dim={args.pq_dim} pq_bits=8 n_lists={n_lists} n_probes={args.n_probes} "
+                               f"batch={args.batch} per GPU k={k}, " + (f"shard-local refinement of {kk} candidates per query and rank" if ratio > 1 else "no refinement"),
+                   "parallelism": f"list shards x{world} dealt by size (LPT), RCCL all-gather of the per-rank top-k",
+                   "transport": "host-staged (mapped file): ranks share devices - functional run, not a scaling figure" if shared_dev
+                                else "RCCL (ncclAllGather / ncclAllReduce over xGMI)",
+                   "oversubscribed": bool(shared_dev), "refine_ratio": ratio,
+                   "rows_on_rank0": len(index), "build_seconds": round(build_s, 1)}}
+    if not args.full:
+        if rank == 0:
+            emit_json(line)
+        return finish_ranks(world, dist, comm)
     scan_ms, ag_ms = C.c_double(0), C.c_double(0)
     n_launch = lib().cuvsAmdProfileCollect(b"pq_scan_kernel", C.byref(scan_ms))
     lib().cuvsAmdProfileCollect(b"shard_all_gather", C.byref(ag_ms))
@@ -597,28 +654,13 @@ def run_c5(args):
             del x, d2
         recall = recall_of(out_i[:ng].cpu().numpy(), best_i.cpu().numpy())
     if rank == 0:
-        ms = elapsed / args.steps * 1e3
         emit_json({
-            "metric": f"QPS, IVF-PQ {rows}x96 int8 list-sharded, batch={args.batch} per GPU", "value": round(nq_total / (ms * 1e-3), 1),
-            "unit": "queries/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": f"u8 codes, {args.lut} LUT, {args.acc} score", "data": "synthetic",
-            "config": {"workload": f"C5 IVF-PQ {rows}x96 int8, pq_dim={args.pq_dim} pq_bits=8 n_lists={n_lists} n_probes={args.n_probes} "
-                                   f"batch={args.batch} per GPU k={k}, " + (f"shard-local refinement of {kk} candidates per query and rank" if ratio > 1 else "no refinement"),
-                       "parallelism": f"list shards x{world} dealt by size (LPT), RCCL all-gather of the per-rank top-k",
-                       "transport": "host-staged (mapped file): ranks share devices - functional run, not a scaling figure" if shared_dev
-                                    else "RCCL (ncclAllGather / ncclAllReduce over xGMI)",
-                       "oversubscribed": bool(shared_dev), "refine_ratio": ratio,
-                       "rows_on_rank0": len(index), "build_seconds": round(build_s, 1)},
+            **line,
             f"recall_at_{k}": None if recall is None else round(recall, 4),
             "scan_kernel_ms_per_step": round(scan_ms.value / max(args.steps, 1), 3), "scan_launches_per_step": n_launch // max(args.steps, 1),
             "all_gather_merge_ms_per_step": round(ag_ms.value / max(args.steps, 1), 3),
             "roofline": roofline, "cpu_baseline": cpu})
-    if world > 1:
-        dist.barrier()
-    comm.close()
-    if world > 1:
-        dist.destroy_process_group()
+    finish_ranks(world, dist, comm)
 
 
 # ---------------------------------------------------------------------------------------------- extra configs (N=1)
@@ -977,7 +1019,7 @@ def extra_c4(res, dev, rows, latent, modes=1, spread=0.35):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rows", type=int, default=100_000_000, help="dataset rows (default = BASELINE config)")
     ap.add_argument("--dim", type=int, default=128)
@@ -1003,6 +1045,12 @@ def main():
     ap.add_argument("--c4-latent", type=int, default=24)
     ap.add_argument("--c4-modes", type=int, default=4096)
     ap.add_argument("--c4-spread", type=float, default=0.7)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline (recall, LUT-scan equality, precisions, metrics, "
+                         "batch sizes, corpora, C1/C2/C4 lines, roofline, PMC passes, CPU baseline); the --no-* options trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the neighbours and distances of the last timed step as DIR/<name>.npy (float64 ids, float32 "
+                         "distances; a fixed, seeded sample of rows above 64 MB)")
     ap.add_argument("--pmc-child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--config", choices=["c3", "c5"], default="c3",
                     help="c3: the headline (IVF-PQ 100M x 128 fp32); c5: IVF-PQ rows x 96 int8 list-sharded over the ranks "
@@ -1019,6 +1067,8 @@ def main():
                          "collectives go through the communicator's host-staged transport (RCCL refuses two ranks on one "
                          "device). Never a scaling figure: the JSON line carries transport / oversubscribed")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.lut == "f32":
         args.acc = "f32"
     if args.pmc_child:
@@ -1105,10 +1155,11 @@ def main():
 
     phase_ms = {}  # per-search HIP-event time of the tail-phase kernels of the last timed() call
 
-    def timed(step, steps, warmup):
+    def timed(step, steps, warmup, profile=True):
+        """wall time of `steps` steps after `warmup`; with `profile`, also the HIP-event kernel times of the library"""
         for _ in range(warmup):
             step()
-        lib().cuvsAmdProfileEnable(1)
+        lib().cuvsAmdProfileEnable(1 if profile else 0)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -1137,8 +1188,51 @@ def main():
         return elapsed, scan_ms.value, n_launch, ag_ms.value
 
     # ------------------------------------------------------------------ timed region (headline variant)
-    elapsed, scan_ms, n_launch, ag_ms = timed(make_step(args.lut, args.acc), args.steps, args.warmup)
+    elapsed, scan_ms, n_launch, ag_ms = timed(make_step(args.lut, args.acc), args.steps, args.warmup, profile=args.full)
     headline_phase_ms = {k: round(v, 3) for k, v in phase_ms.items()}
+    if rank == 0 and args.dump_outputs:
+        if args.refine_ratio > 1:
+            dump_outputs(args.dump_outputs, {"neighbors": neighbors[q_lo:q_hi], "distances": distances[q_lo:q_hi]})
+        else:  # the step returns the search's own first k candidates
+            dump_outputs(args.dump_outputs, {"neighbors": neighbors[q_lo:q_hi],
+                                             "distances": (mrg_d if sharded else cand_d)[q_lo:q_hi, :args.k]})
+
+    total_q = nq_total * args.steps
+    headline = {
+        "metric": "QPS @ recall@10>=0.9, 100Mx128 fp32 IVF-PQ, batch=10k",
+        "value": round(total_q / elapsed, 1),
+        "unit": "queries/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "strong" if strong else "weak",
+        "vs_baseline": None,
+        "dtype": f"u8 codes, {args.lut} LUT, {args.acc} score",
+        "data": "synthetic",
+        "config": {"workload": f"IVF-PQ {args.rows}x{args.dim} fp32, pq_dim={args.pq_dim} pq_bits=8 "
+                               f"n_lists={args.n_lists} n_probes={args.n_probes} batch={args.batch} k={args.k}; rows and held-out queries "
+                               f"from bench.gen_rows (seed 1234 / 4321): Gaussian mixture of 65536 modes ~ N(0, I) in a 32-d latent space, "
+                               f"spread 0.35 per mode, embedded in R^{args.dim} by a fixed random map + N(0, 0.03^2 I) - NOT SURVEY 8d's "
+                               f"generator: the same step on that one is the top-level entry contract_corpus (--full)",
+                   "parallelism": (f"list-sharded index (lists dealt to the {world} ranks by size, LPT), "
+                                   + (f"ONE batch of {args.batch} queries per step searched by every rank on its lists (strong scaling), "
+                                      if strong else f"{world} x {args.batch} queries per step, ")
+                                   + "one native RCCL all-gather of the [Q,k] blocks per step, every rank refines its slice of the batch") if sharded
+                                  else "single GPU",
+                   "lut_dtype": args.lut, "internal_distance_dtype": args.acc, "refine_ratio": args.refine_ratio,
+                   "build_seconds": round(build_s, 1)},
+    }
+    if sharded:
+        headline["config"]["transport"] = ("host-staged (mapped file): ranks share devices - a FUNCTIONAL run of the N-rank path, not a "
+                                           "scaling figure") if shared_dev else "RCCL (ncclAllGather / ncclAllReduce over xGMI)"
+        headline["config"]["oversubscribed"] = bool(shared_dev)
+        headline["config"]["devices_visible"] = torch.cuda.device_count()
+    if not args.full:
+        if rank == 0:
+            emit_json(headline)
+        return finish_ranks(world, dist, comm)
 
     # ------------------------------------------------------------------ recall@10 vs exact search (untimed)
     ng = min(args.gt_queries, q_hi - q_lo)
@@ -1507,55 +1601,16 @@ def main():
         cpu = cpu_baseline_line(dev=dev)  # N > 1: the same bounded CPU leg on rank 0's host cores (the other ranks wait below)
 
     if rank == 0:
-        total_q = nq_total * args.steps
-        out = {
-            "metric": "QPS @ recall@10>=0.9, 100Mx128 fp32 IVF-PQ, batch=10k",
-            "value": round(total_q / elapsed, 1),
-            "unit": "queries/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "strong" if strong else "weak",
-            "vs_baseline": None,
-            "dtype": f"u8 codes, {args.lut} LUT, {args.acc} score",
-            "data": "synthetic",
-            "config": {"workload": f"IVF-PQ {args.rows}x{args.dim} fp32, pq_dim={args.pq_dim} pq_bits=8 "
-                                   f"n_lists={args.n_lists} n_probes={args.n_probes} batch={args.batch} k={args.k}; rows and held-out queries "
-                                   f"from bench.gen_rows (seed 1234 / 4321): Gaussian mixture of 65536 modes ~ N(0, I) in a 32-d latent space, "
-                                   f"spread 0.35 per mode, embedded in R^{args.dim} by a fixed random map + N(0, 0.03^2 I) - NOT SURVEY 8d's "
-                                   f"generator: the same step on that one is the top-level entry contract_corpus",
-                       "parallelism": (f"list-sharded index (lists dealt to the {world} ranks by size, LPT), "
-                                       + (f"ONE batch of {args.batch} queries per step searched by every rank on its lists (strong scaling), "
-                                          if strong else f"{world} x {args.batch} queries per step, ")
-                                       + "one native RCCL all-gather of the [Q,k] blocks per step, every rank refines its slice of the batch") if sharded
-                                      else "single GPU",
-                       "lut_dtype": args.lut, "internal_distance_dtype": args.acc, "refine_ratio": args.refine_ratio,
-                       "build_seconds": round(build_s, 1), "variants": variants, "metric_variants": metric_variants,
-                       "sharded_one_rank": sharded_line, "corpus_variants": corpus_variants, "batch_sweep": batch_sweep},
-            "recall_at_10": round(recall, 4),
-            "contract_corpus": contract_corpus,
-            "scan3_equals_lut_scan": scan3_equals_lut_scan,
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            "extra": extra,
-        }
+        headline["config"].update({"variants": variants, "metric_variants": metric_variants, "sharded_one_rank": sharded_line,
+                                   "corpus_variants": corpus_variants, "batch_sweep": batch_sweep})
+        headline.update({"recall_at_10": round(recall, 4), "contract_corpus": contract_corpus, "scan3_equals_lut_scan": scan3_equals_lut_scan,
+                         "roofline": roofline, "cpu_baseline": cpu, "extra": extra})
         if sharded:
-            out["config"]["all_gather_ms_per_step"] = round(ag_ms / max(args.steps, 1), 3)
-            out["config"]["transport"] = ("host-staged (mapped file): ranks share devices - a FUNCTIONAL run of the N-rank path, not a "
-                                          "scaling figure") if shared_dev else "RCCL (ncclAllGather / ncclAllReduce over xGMI)"
-            out["config"]["oversubscribed"] = bool(shared_dev)
-            out["config"]["devices_visible"] = torch.cuda.device_count()
+            headline["config"]["all_gather_ms_per_step"] = round(ag_ms / max(args.steps, 1), 3)
         # RCCL writes its start-up banner through C stdio (the one-rank sharded line initialises a communicator): it goes to stderr,
         # the JSON line is the ONLY line on stdout
-        emit_json(out)
-    if world > 1:
-        dist.barrier()  # rank 0 may still be in its CPU leg: nobody tears the communicators down under it
-    if comm is not None:
-        comm.close()
-    if world > 1:
-        dist.destroy_process_group()
+        emit_json(headline)
+    finish_ranks(world, dist, comm)
 
 
 if __name__ == "__main__":

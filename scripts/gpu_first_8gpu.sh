@@ -41,7 +41,7 @@ for N in 1 2 4 8; do
   for MODE in weak strong; do
     [ "$N" = 1 ] && [ "$MODE" = strong ] && continue
     EXTRA="--no-variants --no-extras --no-pmc"; [ "$N" = 1 ] && EXTRA="--no-extras"
-    if timeout 1500 python bench.py --gpus "$N" --scaling "$MODE" --rows "$ROWS" --steps 20 --warmup 3 $EXTRA > "$OUT/bench_n${N}_$MODE.json" 2> "$OUT/bench_n${N}_$MODE.log"; then
+    if timeout 1500 python bench.py --full --gpus "$N" --scaling "$MODE" --rows "$ROWS" --steps 20 --warmup 3 $EXTRA > "$OUT/bench_n${N}_$MODE.json" 2> "$OUT/bench_n${N}_$MODE.log"; then
       tail -1 "$OUT/bench_n${N}_$MODE.json" | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print("[first-contact] N=%d %s: %.0f q/s, %.3f ms per step, recall %.4f" % (d["n_gpus"], d["scaling"], d["value"], d["ms_per_step"], d["recall_at_10"]))' | tee -a "$OUT/summary.txt"
     else
       echo "[first-contact] bench N=$N $MODE FAILED (see $OUT/bench_n${N}_$MODE.log)" | tee -a "$OUT/summary.txt"
