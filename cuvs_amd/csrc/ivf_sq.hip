@@ -1,0 +1,1248 @@
+// IVF-SQ on MI355X: index build/extend, list-major scan over 8-bit scalar-quantized rows, C ABI (drop-in for
+// c/src/neighbors/ivf_sq.cpp).
+//
+// Reference: cpp/src/neighbors/ivf_sq/ivf_sq_build.cuh (training of the per-dimension quantizer on the residuals of a
+// row sample, encoding), ivf_sq_search.cuh + detail/jit_lto_kernels (scan arithmetic), ivf_sq_serialize.cuh (file),
+// cpp/include/cuvs/neighbors/ivf_sq.hpp (list layout of the file: 32-row groups of 16-byte chunks).
+//
+// MI355X design (the schedule of ivf_flat.hip): all lists in one flat allocation, rows in tiles of 64 (one wave64 lane
+// per row), [tile][chunk][lane] x 16 codes, the dimension padded to 16 with code 0 -> one chunk load of a wave is 1 KiB
+// and coalesced. (query, probe) pairs grouped by list, up to 8 queries per work item share one pass over the list's
+// codes; a lane converts every code byte to fp32 once and applies it to all queries of the item. The per-pair query
+// terms ([dim_pad][8] fp32 per item) and the per-dimension quantizer values are read with wave-uniform addresses
+// (scalar cache -> SGPRs). Per-wave register top lists with shared k-th bounds (k <= 256), or every score written out
+// and selected (k > 256). DESIGN 3.2 has the arithmetic contract.
+#include "ivf_common.hpp"
+#include "npy_io.hpp"
+
+#include <cuvs/neighbors/ivf_sq.h>
+
+#include <algorithm>
+#include <cfloat>
+#include <numeric>
+#include <random>
+#include <type_traits>
+
+namespace cuvs_amd {
+
+void load_range_as_float(resources& res, const void* data, elem_t et, bool is_host, int64_t dim, int64_t r0,
+                         int64_t cnt, float* out);
+void load_gather_as_float(resources& res, const void* data, elem_t et, bool is_host, int64_t dim,
+                          const uint32_t* d_ids, int64_t cnt, float* out);
+
+struct ivf_sq_index {
+  int metric   = 0;
+  elem_t dtype = elem_t::f32;  // element type of the rows the index was built from (f32 / f16)
+  bool conservative_memory_allocation = false;
+  uint32_t n_lists = 0, dim = 0;
+  uint32_t n_chunks = 0;  // 16-code chunks per row (dim padded to 16)
+  int64_t size = 0, padded_rows = 0;
+  dev_buf<float> centers;            // [n_lists, dim]
+  dev_buf<float> center_norms;       // [n_lists] canonical |c|^2
+  dev_buf<float> center_norms_sqrt;  // [n_lists] |c| (cosine only)
+  dev_buf<float> vmin, delta;        // [dim] the scalar quantizer
+  dev_buf<uint8_t> data;             // [padded_rows / 64, n_chunks, 64, 16 codes]
+  dev_buf<int64_t> indices;          // [padded_rows]
+  dev_buf<uint32_t> list_sizes, list_offsets;
+  std::vector<uint32_t> h_list_sizes, h_list_offsets;
+};
+
+namespace {
+
+constexpr int kSqThreads = 512;
+constexpr int kSqWaves   = kSqThreads / 64;
+constexpr int kSqQPB     = 8;
+constexpr int kSqStop    = 4;  // chunk loads issued 4 at a time (dot products)
+
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
+
+inline bool sq_metric_ok(int m)
+{
+  return m == M_L2Expanded || m == M_L2SqrtExpanded || m == M_InnerProduct || m == M_CosineExpanded;
+}
+
+// ------------------------------------------------------------------ training of the quantizer
+// residual of every sample row against its centre, in place; fp16 data: rounded back to fp16 (the reference keeps the
+// training residuals in the element type)
+__global__ void sq_residuals_kernel(float* __restrict__ x, const float* __restrict__ centers, const uint32_t* __restrict__ labels,
+                                    int64_t n, uint32_t dim, int round_half)
+{
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n * dim) return;
+  const int64_t i = t / dim;
+  const uint32_t d = (uint32_t)(t % dim);
+  float r = x[t] - centers[(size_t)labels[i] * dim + d];
+  if (round_half) r = __half2float(__float2half_rn(r));
+  x[t] = r;
+}
+
+// per-dimension min / max: workgroup b takes a run of rows, thread t the dimensions t, t + 256, ... (coalesced row reads);
+// partials [blocks, dim] reduced by sq_quantizer_kernel (min / max are exact in any order)
+constexpr int kMinMaxBlocks = 256;
+__global__ __launch_bounds__(256) void sq_minmax_partial_kernel(const float* __restrict__ x, int64_t n, uint32_t dim,
+                                                                float* __restrict__ pmin, float* __restrict__ pmax)
+{
+  const int64_t per = (n + gridDim.x - 1) / gridDim.x;
+  const int64_t r0 = (int64_t)blockIdx.x * per, r1 = min(n, r0 + per);
+  for (uint32_t d = threadIdx.x; d < dim; d += blockDim.x) {
+    float lo = FLT_MAX, hi = -FLT_MAX;
+    for (int64_t r = r0; r < r1; ++r) {
+      const float v = x[(size_t)r * dim + d];
+      lo = fminf(lo, v);
+      hi = fmaxf(hi, v);
+    }
+    pmin[(size_t)blockIdx.x * dim + d] = lo;
+    pmax[(size_t)blockIdx.x * dim + d] = hi;
+  }
+}
+
+// ivf_sq_build.cuh: margin = 5 % of the range on both sides; 255 steps over the widened range; empty range: step 1
+__global__ void sq_quantizer_kernel(const float* __restrict__ pmin, const float* __restrict__ pmax, int blocks, uint32_t dim,
+                                    float* __restrict__ vmin, float* __restrict__ delta)
+{
+  const uint32_t d = blockIdx.x * blockDim.x + threadIdx.x;
+  if (d >= dim) return;
+  float lo = FLT_MAX, hi = -FLT_MAX;
+  for (int b = 0; b < blocks; ++b) {
+    lo = fminf(lo, pmin[(size_t)b * dim + d]);
+    hi = fmaxf(hi, pmax[(size_t)b * dim + d]);
+  }
+  const float range  = hi - lo;
+  const float margin = range * 0.05f;
+  delta[d] = range > 0.0f ? (range + 2.0f * margin) / 255.0f : 1.0f;
+  vmin[d]  = lo - margin;
+}
+
+// ------------------------------------------------------------------ encoding (extend)
+struct sq_pack_args {
+  const void* src;           // rows [*, dim] of T
+  const uint32_t* perm;      // new-row ids sorted by (list, row)
+  const uint32_t* labels;
+  const uint32_t* new_off;
+  const uint32_t* old_sizes;
+  const uint32_t* list_off;
+  const int64_t* new_ids;
+  const float* centers;
+  const float* vmin;
+  const float* delta;
+  int64_t id_base, j0, batch;
+  int src_is_batch;          // 1: src holds rows j0.. in sorted order (host staging); 0: src is the full device array
+  uint32_t dim, n_chunks;
+  uint8_t* data;
+  int64_t* indices;
+};
+
+// code = clamp(round((x - c - vmin) / delta), 0, 255): fp32 subtraction, correctly rounded division, half away from zero
+__device__ inline uint8_t sq_encode(float x, float c, float vmin, float delta)
+{
+  const float val  = x - c;
+  const float code = roundf((val - vmin) / delta);
+  return (uint8_t)fminf(fmaxf(code, 0.0f), 255.0f);
+}
+
+// one thread per (sorted row, chunk of 16 dimensions): 16 codes -> one 16-byte store at the row's slot
+template <typename T>
+__global__ void sq_pack_kernel(sq_pack_args a)
+{
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= a.batch * a.n_chunks) return;
+  const int64_t jb  = t / a.n_chunks;
+  const uint32_t ch = (uint32_t)(t % a.n_chunks);
+  const int64_t j   = a.j0 + jb;
+  const uint32_t row = a.perm[j];
+  const uint32_t L   = a.labels[row];
+  const int64_t fr   = (int64_t)a.list_off[L] + a.old_sizes[L] + (j - (int64_t)a.new_off[L]);
+  const T* src       = static_cast<const T*>(a.src) + (a.src_is_batch ? jb : (int64_t)row) * a.dim;
+  const float* c     = a.centers + (size_t)L * a.dim;
+  alignas(16) uint8_t codes[16];
+#pragma unroll
+  for (uint32_t e = 0; e < 16; ++e) {
+    const uint32_t d = ch * 16 + e;
+    codes[e]         = d < a.dim ? sq_encode(to_float(src[d]), c[d], a.vmin[d], a.delta[d]) : (uint8_t)0;
+  }
+  const size_t addr = (((size_t)(fr >> 6) * a.n_chunks + ch) * 64 + (size_t)(fr & 63)) * 16;
+  *reinterpret_cast<uint4*>(a.data + addr) = *reinterpret_cast<const uint4*>(codes);
+  if (ch == 0) a.indices[fr] = a.new_ids ? a.new_ids[row] : a.id_base + (int64_t)row;
+}
+
+__global__ void sq_relocate_lists_kernel(const uint8_t* __restrict__ old_data, const int64_t* __restrict__ old_ids,
+                                         const uint32_t* __restrict__ old_off, const uint32_t* __restrict__ old_sizes,
+                                         const uint32_t* __restrict__ new_off, uint32_t n_chunks, uint8_t* __restrict__ data,
+                                         int64_t* __restrict__ ids)
+{
+  const uint32_t L  = blockIdx.x;
+  const uint32_t sz = old_sizes[L];
+  const int64_t so = old_off[L], dn = new_off[L];
+  for (uint32_t i = threadIdx.x; i < sz; i += blockDim.x) ids[dn + i] = old_ids[so + i];
+  const size_t n16 = (size_t)((sz + 63) / 64) * n_chunks * 64;
+  const uint4* s = reinterpret_cast<const uint4*>(old_data + (size_t)(so >> 6) * n_chunks * 1024);
+  uint4* dd      = reinterpret_cast<uint4*>(data + (size_t)(dn >> 6) * n_chunks * 1024);
+  for (size_t i = threadIdx.x; i < n16; i += blockDim.x) dd[i] = s[i];
+}
+
+__global__ void sq_zero_norms_kernel(float* p, int n)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) p[i] = 0.f;
+}
+
+// ------------------------------------------------------------------ search
+// per-dimension step (padded dims: 1) and, for dot products, aux[L][d] = c_d + vmin_d of every list (padded dims: 0).
+// With a zero query term and code 0 a padded dimension adds exactly nothing to any score.
+__global__ void sq_search_terms_kernel(const float* __restrict__ centers, const float* __restrict__ vmin,
+                                       const float* __restrict__ delta, uint32_t n_lists, uint32_t dim, uint32_t dim_pad,
+                                       int with_aux, float* __restrict__ delta_pad, float* __restrict__ aux)
+{
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < dim_pad) delta_pad[t] = t < dim ? delta[t] : 1.0f;
+  if (!with_aux || t >= (int64_t)n_lists * dim_pad) return;
+  const uint32_t L = (uint32_t)(t / dim_pad), d = (uint32_t)(t % dim_pad);
+  aux[t] = d < dim ? centers[(size_t)L * dim + d] + vmin[d] : 0.0f;
+}
+
+// Query terms of every work item, [dim_pad][QPB] fp32 + one row of |q| (cosine). L2: (q_d - vmin_d) - c_d of the item's list;
+// dot products: q_d. Queries are the batch's fp32 copy (qf).
+__global__ void sq_query_tiles_kernel(const work_item* __restrict__ items, const uint32_t* __restrict__ n_items,
+                                      const uint32_t* __restrict__ sorted_pairs, const float* __restrict__ qf,
+                                      const float* __restrict__ qnorm, const float* __restrict__ centers,
+                                      const float* __restrict__ vmin, uint32_t n_probes, uint32_t n_lists, uint32_t dim,
+                                      uint32_t dim_pad, int is_l2, float* __restrict__ tiles)
+{
+  constexpr int QPB = kSqQPB;
+  const uint32_t w = blockIdx.x;
+  if (w >= *n_items) return;
+  const work_item item = items[w];
+  const uint32_t L     = item.list >= n_lists ? item.list - n_lists : item.list;
+  __shared__ uint32_t qid[QPB];
+  if (threadIdx.x < QPB)
+    qid[threadIdx.x] = threadIdx.x < item.count ? sorted_pairs[item.first + threadIdx.x] / n_probes : 0xffffffffu;
+  __syncthreads();
+  float* out = tiles + (size_t)w * (dim_pad + 1) * QPB;
+  for (uint32_t t = threadIdx.x; t < dim_pad * QPB; t += blockDim.x) {
+    const uint32_t d = t / QPB, j = t % QPB;
+    float v = 0.f;
+    if (qid[j] != 0xffffffffu && d < dim) {
+      v = qf[(size_t)qid[j] * dim + d];
+      if (is_l2) v = (v - vmin[d]) - centers[(size_t)L * dim + d];
+    }
+    out[t] = v;
+  }
+  if (threadIdx.x < QPB)
+    out[(size_t)dim_pad * QPB + threadIdx.x] = (qnorm != nullptr && qid[threadIdx.x] != 0xffffffffu) ? qnorm[qid[threadIdx.x]] : 0.f;
+}
+
+struct sq_scan_args {
+  const work_item* items;
+  const uint32_t* item_begin;  // device scalars: this launch covers items [*item_begin, *item_end); nullptr: from 0
+  const uint32_t* item_end;
+  uint32_t n_lists;            // item.list >= n_lists: tail-phase label of list item.list - n_lists
+  const uint32_t* sorted_pairs;
+  const float* qtiles;         // [n_items, dim_pad + 1, QPB]
+  const float* delta_pad;      // [dim_pad]
+  const float* aux;            // [n_lists, dim_pad] (dot products)
+  const uint8_t* data;
+  const uint32_t* list_offsets;
+  const uint32_t* list_sizes;
+  float* out_d;
+  uint32_t* out_i;
+  uint32_t* query_kth;
+  const uint32_t* filter_bits;  // optional bitset over source ids (1 keeps)
+  const int64_t* indices;
+  uint32_t n_probes, n_chunks, k;
+  float* all_scores;            // non-fused path (k > 256): [n_queries, scores_ld] score of every probed row
+  uint32_t* all_rows;           //   flat row of every column
+  const uint32_t* pair_seg;     //   first column of each pair in its query's row
+  size_t scores_ld;
+};
+
+// keeps the four chunk loads of a group issued back to back (see ivf_flat.hip keep_loads_together)
+__device__ inline void sq_keep_loads_together(uint4 (&w)[kSqStop])
+{
+  asm(""
+      : "+v"(w[0].x), "+v"(w[0].y), "+v"(w[0].z), "+v"(w[0].w), "+v"(w[1].x), "+v"(w[1].y), "+v"(w[1].z), "+v"(w[1].w),
+        "+v"(w[2].x), "+v"(w[2].y), "+v"(w[2].z), "+v"(w[2].w), "+v"(w[3].x), "+v"(w[3].y), "+v"(w[3].z), "+v"(w[3].w));
+}
+
+// METRIC 0: L2 (both variants), 1: inner product, 2: cosine. ALL: the non-fused path (every score written out).
+// Per (pair, dim): L2 diff = fma(-code, delta_d, qt_d), acc = fma(diff, diff, acc); dot products v = fma(code, delta_d, aux_d)
+// once per (row, dim), acc = fma(q_d, v, acc) per pair (cosine: vn = fma(v, v, vn) once per row). Scores: smaller is better
+// (inner product negated; cosine 1 - acc / (|q| sqrt(vn))).
+template <int E, int METRIC, bool ALL = false>
+__global__ __launch_bounds__(kSqThreads) void ivf_sq_scan_kernel(sq_scan_args a)
+{
+  constexpr int QPB = kSqQPB;
+  constexpr bool IP = METRIC != 0;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const uint32_t item0 = a.item_begin ? *a.item_begin : 0u;
+  const uint32_t w     = item0 + blockIdx.x;
+  if (w >= *a.item_end) return;
+  const work_item item = a.items[w];
+
+  const uint32_t dim_pad = a.n_chunks * 16;
+  const size_t off = (((size_t)QPB * kSqWaves * a.k * 8) + 15) & ~size_t(15);  // merge area
+  uint32_t* kthb = reinterpret_cast<uint32_t*>(smem + off);
+  uint32_t* pid  = kthb + 16;
+
+  const int tid  = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const uint32_t L        = item.list >= a.n_lists ? item.list - a.n_lists : item.list;
+  const uint32_t base_row = a.list_offsets[L];
+  const uint32_t len      = a.list_sizes[L];
+
+  if (tid < QPB) {
+    const uint32_t p = tid < (int)item.count ? a.sorted_pairs[item.first + tid] : 0xffffffffu;
+    pid[tid]         = p;
+    kthb[tid]        = p != 0xffffffffu ? a.query_kth[p / a.n_probes] : 0u;
+  }
+  __syncthreads();
+  // wave-uniform pointers: scalar loads
+  const float* __restrict__ qt  = a.qtiles + (size_t)w * (dim_pad + 1) * QPB;
+  const float* __restrict__ dl  = a.delta_pad;
+  const float* __restrict__ aux = IP ? a.aux + (size_t)L * dim_pad : nullptr;
+
+  wave_top<E> top[QPB];
+#pragma unroll
+  for (int j = 0; j < QPB; ++j) top[j].init();
+  const int kr          = (int)a.k - 1;
+  uint32_t fresh        = 0xffu;  // bit j: this wave's list of query j is still empty (wave-uniform)
+  const size_t g0       = (size_t)(base_row >> 6);
+  const uint4* data16   = reinterpret_cast<const uint4*>(a.data);
+  const uint32_t n_tile = (len + 63) / 64;
+
+  for (uint32_t tile = wave; tile < n_tile; tile += kSqWaves) {
+    const uint32_t tile0 = tile * 64;
+    const uint32_t v     = tile0 + lane;
+    const bool valid     = v < len;
+    f32x2_t accv[QPB / 2];
+#pragma unroll
+    for (int j = 0; j < QPB / 2; ++j) accv[j] = f32x2_t{0.f, 0.f};
+    float vn = 0.f;  // cosine: |v|^2 of this lane's decoded row
+    const uint4* cp = data16 + ((g0 + tile) * a.n_chunks) * 64 + lane;
+    float bf[QPB];  // L2 early stop: the k-th bounds at the start of the tile (they only decrease)
+#pragma unroll
+    for (int j = 0; j < QPB; ++j) {
+      const uint32_t kk = __builtin_amdgcn_readfirstlane(kthb[j]);
+      bf[j] = (IP || j >= (int)item.count) ? -INFINITY : (kk >= 0xff800000u ? INFINITY : key_to_float(kk));
+    }
+    auto chunk_step = [&](const uint4& cw, const uint32_t ch) {
+      const uint32_t words[4] = {cw.x, cw.y, cw.z, cw.w};
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const uint32_t d = ch * 16 + (uint32_t)e;
+        const float x    = (float)((words[e >> 2] >> (8 * (e & 3))) & 0xffu);  // v_cvt_f32_ubyteN
+        const float* qr  = qt + (size_t)d * QPB;
+        const f32x2_t qv[QPB / 2] = {f32x2_t{qr[0], qr[1]}, f32x2_t{qr[2], qr[3]}, f32x2_t{qr[4], qr[5]}, f32x2_t{qr[6], qr[7]}};
+        const float dd = dl[d];
+        if constexpr (!IP) {
+          const f32x2_t nx = f32x2_t{-x, -x}, dv = f32x2_t{dd, dd};
+#pragma unroll
+          for (int j = 0; j < QPB / 2; ++j) {
+            const f32x2_t t = __builtin_elementwise_fma(nx, dv, qv[j]);
+            accv[j]         = __builtin_elementwise_fma(t, t, accv[j]);
+          }
+        } else {
+          const float y    = __fmaf_rn(x, dd, aux[d]);
+          const f32x2_t yy = f32x2_t{y, y};
+          if (METRIC == 2) vn = __fmaf_rn(y, y, vn);
+#pragma unroll
+          for (int j = 0; j < QPB / 2; ++j) accv[j] = __builtin_elementwise_fma(qv[j], yy, accv[j]);
+        }
+      }
+    };
+    if constexpr (IP) {
+      for (uint32_t ch0 = 0; ch0 < a.n_chunks; ch0 += kSqStop) {
+        uint4 cws[kSqStop];  // padded rows of a tile are zero-filled: always readable
+#pragma unroll
+        for (int c = 0; c < kSqStop; ++c) cws[c] = cp[(size_t)min(ch0 + (uint32_t)c, a.n_chunks - 1u) * 64];
+        sq_keep_loads_together(cws);
+#pragma unroll
+        for (int c = 0; c < kSqStop; ++c) {
+          const uint32_t ch = ch0 + (uint32_t)c;
+          if (ch >= a.n_chunks) break;  // wave-uniform
+          chunk_step(cws[c], ch);
+        }
+      }
+    } else {
+      for (uint32_t ch = 0; ch < a.n_chunks; ++ch) {
+        if (!ALL && ch > 0) {
+          // partial sums of squares only grow: once every row of the tile is above every query's bound, stop (tested after
+          // every chunk: a chunk holds 16 dimensions here, four times IVF-Flat's fp32 chunk)
+          bool below = false;
+#pragma unroll
+          for (int j = 0; j < QPB; ++j) below = below || (accv[j >> 1][j & 1] <= bf[j]);
+          if (__ballot(valid && below) == 0ull) break;  // wave-uniform
+        }
+        chunk_step(cp[(size_t)ch * 64], ch);
+      }
+    }
+    float acc[QPB];
+#pragma unroll
+    for (int j = 0; j < QPB; ++j) acc[j] = accv[j >> 1][j & 1];
+    if (METRIC == 2) {
+      const float xn = sqrtf(vn);
+#pragma unroll
+      for (int j = 0; j < QPB; ++j) {
+        const float denom = qt[(size_t)dim_pad * QPB + j] * xn;
+        acc[j]            = denom > 0.0f ? 1.0f - acc[j] / denom : 0.0f;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < QPB; ++j) {
+      if (j >= (int)item.count) break;
+      const float dj = METRIC == 1 ? -acc[j] : acc[j];  // smaller is better
+      if constexpr (ALL) {
+        bool keep = valid;
+        if (keep && a.filter_bits != nullptr) {
+          const int64_t sid = a.indices[(size_t)base_row + v];
+          keep              = (a.filter_bits[sid >> 5] >> (sid & 31)) & 1u;
+        }
+        const uint32_t p = pid[j];
+        if (keep) {
+          const size_t o  = (size_t)(p / a.n_probes) * a.scores_ld + a.pair_seg[p] + v;
+          a.all_scores[o] = dj;
+          a.all_rows[o]   = base_row + v;
+        }
+        continue;
+      }
+      const uint32_t bound = kthb[j];
+      unsigned long long m = __ballot(valid && float_to_key(dj) <= bound);
+      if (m == 0ull) continue;
+      const bool first = ((fresh >> j) & 1u) != 0u;
+      fresh &= ~(1u << j);
+      if (first && a.filter_bits == nullptr && __popcll(m) >= 12 && __ballot(dj != dj) == 0ull) {
+        // the wave's first candidates of query j: one sorting network instead of up to 64 serial insertions
+        const bool c = ((m >> lane) & 1ull) != 0ull;
+        float sd     = c ? dj : INFINITY;
+        uint32_t si  = c ? tile0 + (uint32_t)lane : 0xffffffffu;
+        wave_sort64(sd, si, lane);
+        top[j].d[0] = sd;
+        top[j].i[0] = si;
+        const float kd0 = top[j].rank_d(kr);
+        if (lane == 0 && kd0 < INFINITY) atomicMin(&kthb[j], float_to_key(kd0));
+        continue;
+      }
+      float kd      = top[j].rank_d(kr);
+      uint32_t ki   = top[j].rank_i(kr);
+      bool improved = false;
+      while (m != 0ull) {
+        const int src = (int)__ffsll((long long)m) - 1;
+        m &= m - 1ull;
+        const float cd    = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(dj), src));
+        const uint32_t ci = tile0 + (uint32_t)src;
+        if (a.filter_bits != nullptr) {
+          const int64_t sid = a.indices[(size_t)base_row + ci];
+          if (!((a.filter_bits[sid >> 5] >> (sid & 31)) & 1u)) continue;
+        }
+        if ((cd < kd) || (cd == kd && ci < ki)) {
+          top[j].insert(cd, ci, lane);
+          kd       = top[j].rank_d(kr);
+          ki       = top[j].rank_i(kr);
+          improved = true;
+        }
+      }
+      if (improved && lane == 0 && kd < INFINITY) atomicMin(&kthb[j], float_to_key(kd));
+    }
+  }
+
+  if constexpr (ALL) return;
+  // ---- merge the wave lists
+  __syncthreads();
+  if constexpr (E > 1) {
+    constexpr int KP2 = E == 2 ? 128 : 256;
+    float* sd    = reinterpret_cast<float*>(smem);
+    uint32_t* si = reinterpret_cast<uint32_t*>(smem + (size_t)kSqWaves * KP2 * 4);
+    for (int j = 0; j < QPB; ++j) {
+      if (j >= (int)item.count) break;  // workgroup-uniform
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        const int r   = e * 64 + lane;
+        const bool in = r < (int)a.k;
+        sd[wave * KP2 + r] = in ? top[j].d[e] : INFINITY;
+        si[wave * KP2 + r] = in ? top[j].i[e] : 0xffffffffu;
+      }
+      __syncthreads();
+      merge_sorted_lists<kSqThreads>(sd, si, kSqWaves, KP2, tid);
+      const size_t o = (size_t)pid[j] * a.k;
+      for (int r = tid; r < (int)a.k; r += kSqThreads) {
+        const bool ok  = si[r] != 0xffffffffu;
+        a.out_d[o + r] = ok ? sd[r] : FLT_MAX;
+        a.out_i[o + r] = ok ? base_row + si[r] : 0xffffffffu;
+      }
+      if (tid == 0 && si[a.k - 1] != 0xffffffffu && sd[a.k - 1] < INFINITY)
+        atomicMin(&a.query_kth[pid[j] / a.n_probes], float_to_key(sd[a.k - 1]));
+      __syncthreads();  // the next query reuses the area
+    }
+    return;
+  }
+  float* mg_d    = reinterpret_cast<float*>(smem);
+  uint32_t* mg_i = reinterpret_cast<uint32_t*>(smem + (size_t)QPB * kSqWaves * a.k * 4);
+#pragma unroll
+  for (int j = 0; j < QPB; ++j) {
+    const int r = lane;
+    if (r < (int)a.k) {
+      mg_d[((size_t)j * kSqWaves + wave) * a.k + r] = top[j].d[0];
+      mg_i[((size_t)j * kSqWaves + wave) * a.k + r] = top[j].i[0];
+    }
+  }
+  __syncthreads();
+  if (wave < QPB && wave < (int)item.count) {
+    const int j = wave;
+    wave_top<1> fin;
+    fin.init();
+    float kd    = INFINITY;
+    uint32_t ki = 0xffffffffu;
+    const int n = kSqWaves * (int)a.k;
+    for (int b0 = 0; b0 < n; b0 += 64) {
+      float md    = INFINITY;
+      uint32_t mi = 0xffffffffu;
+      if (b0 + lane < n) { md = mg_d[(size_t)j * n + b0 + lane]; mi = mg_i[(size_t)j * n + b0 + lane]; }
+      unsigned long long m = __ballot(mi != 0xffffffffu && ((md < kd) || (md == kd && mi < ki)));
+      while (m != 0ull) {
+        const int src = (int)__ffsll((long long)m) - 1;
+        m &= m - 1ull;
+        const float cd    = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(md), src));
+        const uint32_t ci = __builtin_amdgcn_readlane(mi, src);
+        if ((cd < kd) || (cd == kd && ci < ki)) {
+          fin.insert(cd, ci, lane);
+          kd = fin.rank_d(kr);
+          ki = fin.rank_i(kr);
+        }
+      }
+    }
+    const size_t o = (size_t)pid[j] * a.k;
+    if (lane < (int)a.k) {
+      const bool ok     = fin.i[0] != 0xffffffffu;
+      a.out_d[o + lane] = ok ? fin.d[0] : FLT_MAX;
+      a.out_i[o + lane] = ok ? base_row + fin.i[0] : 0xffffffffu;
+    }
+    if (lane == 0 && kd < INFINITY) atomicMin(&a.query_kth[pid[j] / a.n_probes], float_to_key(kd));
+  }
+}
+
+__global__ void sq_postprocess_kernel(const uint32_t* __restrict__ pos, const float* __restrict__ d_in, int64_t n,
+                                      const int64_t* __restrict__ indices, int metric, int64_t* __restrict__ neighbors,
+                                      float* __restrict__ distances)
+{
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t p = pos[i];
+  neighbors[i]     = p == 0xffffffffu ? INT64_MAX : indices[p];
+  float d          = d_in[i];
+  if (p == 0xffffffffu) d = FLT_MAX;
+  else if (metric == M_InnerProduct) d = -d;
+  else if (metric == M_L2SqrtExpanded) d = sqrtf(d);
+  distances[i] = d;
+}
+
+// one list's codes row-major [n_rows, dim] (test export)
+__global__ void sq_unpack_list_kernel(const uint8_t* __restrict__ data, uint32_t n_chunks, uint32_t dim, int64_t flat_row0,
+                                      uint32_t n_rows, uint8_t* __restrict__ out)
+{
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)n_rows * dim) return;
+  const int64_t fr = flat_row0 + i / dim;
+  const uint32_t d = (uint32_t)(i % dim);
+  out[i] = data[(((size_t)(fr >> 6) * n_chunks + d / 16) * 64 + (size_t)(fr & 63)) * 16 + d % 16];
+}
+
+template <int E, int METRIC, bool ALL = false>
+void launch_sq_scan_kern(resources& res, const sq_scan_args& a, size_t smem, unsigned grid)
+{
+  auto kern = ivf_sq_scan_kernel<E, METRIC, ALL>;
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(kSqThreads), smem, res.stream, a);
+}
+
+void launch_sq_scan(resources& res, const sq_scan_args& a, int metric_kind, size_t smem, unsigned grid, bool big_k)
+{
+  profile_begin(res, "ivf_sq_scan_kernel");
+  if (a.all_scores != nullptr) {
+    if (metric_kind == 2)      launch_sq_scan_kern<1, 2, true>(res, a, smem, grid);
+    else if (metric_kind == 1) launch_sq_scan_kern<1, 1, true>(res, a, smem, grid);
+    else                       launch_sq_scan_kern<1, 0, true>(res, a, smem, grid);
+  } else if (big_k) {
+    if (metric_kind == 2)      launch_sq_scan_kern<4, 2>(res, a, smem, grid);
+    else if (metric_kind == 1) launch_sq_scan_kern<4, 1>(res, a, smem, grid);
+    else                       launch_sq_scan_kern<4, 0>(res, a, smem, grid);
+  } else {
+    if (metric_kind == 2)      launch_sq_scan_kern<1, 2>(res, a, smem, grid);
+    else if (metric_kind == 1) launch_sq_scan_kern<1, 1>(res, a, smem, grid);
+    else                       launch_sq_scan_kern<1, 0>(res, a, smem, grid);
+  }
+  profile_end(res, "ivf_sq_scan_kernel");
+  HIP_TRY(hipGetLastError());
+}
+
+// list labels of fp32 rows with the index metric (the rule of ivf_flat_extend): L2 argmin; inner product: the largest dot
+// product (|c|^2 term dropped); cosine: L2 on unit-length copies (x is normalised in place)
+void sq_predict(resources& res, const ivf_sq_index& idx, float* x, int64_t cnt, const float* zero_norms, uint32_t* labels)
+{
+  if (idx.metric == M_CosineExpanded) normalize_rows(res, x, cnt, idx.dim);
+  const float* norms = idx.metric == M_InnerProduct ? zero_norms : idx.center_norms.data();
+  fused_l2_argmin<float>(res, x, cnt, idx.dim, idx.centers.data(), idx.n_lists, idx.dim, norms, labels, nullptr);
+}
+
+void sq_set_center_norms(resources& res, ivf_sq_index& idx)
+{
+  idx.center_norms = dev_buf<float>::persistent(idx.n_lists);
+  row_norms<float>(res, idx.centers.data(), idx.n_lists, idx.dim, idx.dim, idx.center_norms.data(), false);
+  if (idx.metric == M_CosineExpanded) {
+    idx.center_norms_sqrt = dev_buf<float>::persistent(idx.n_lists);
+    row_norms<float>(res, idx.centers.data(), idx.n_lists, idx.dim, idx.dim, idx.center_norms_sqrt.data(), true);
+  }
+}
+
+std::unique_ptr<ivf_sq_index> sq_empty_index(resources& res, int metric, uint32_t n_lists, uint32_t dim, bool cma)
+{
+  auto idx      = std::make_unique<ivf_sq_index>();
+  idx->metric   = metric;
+  idx->n_lists  = n_lists;
+  idx->dim      = dim;
+  idx->n_chunks = (dim + 15) / 16;
+  idx->conservative_memory_allocation = cma;
+  idx->centers      = dev_buf<float>::persistent((size_t)n_lists * dim);
+  idx->vmin         = dev_buf<float>::persistent(dim);
+  idx->delta        = dev_buf<float>::persistent(dim);
+  idx->list_sizes   = dev_buf<uint32_t>::persistent(n_lists);
+  idx->list_offsets = dev_buf<uint32_t>::persistent(n_lists + 1);
+  HIP_TRY(hipMemsetAsync(idx->list_sizes.data(), 0, idx->list_sizes.bytes(), res.stream));
+  HIP_TRY(hipMemsetAsync(idx->list_offsets.data(), 0, idx->list_offsets.bytes(), res.stream));
+  idx->h_list_sizes.assign(n_lists, 0);
+  idx->h_list_offsets.assign(n_lists + 1, 0);
+  return idx;
+}
+
+}  // namespace
+
+void ivf_sq_extend(resources& res, ivf_sq_index& idx, const void* data, elem_t et, int64_t n_new, bool is_host,
+                   const int64_t* new_ids, bool ids_on_host)
+{
+  if (n_new == 0) return;
+  CUVS_EXPECTS(et == elem_t::f32 || et == elem_t::f16, "ivf_sq::extend: vectors must be float32 or float16");
+  CUVS_EXPECTS(new_ids != nullptr || idx.size == 0, "You must pass data indices when the index is non-empty.");
+  CUVS_EXPECTS(idx.size + n_new < (int64_t(1) << 32) - 64 * (int64_t)idx.n_lists, "index too large for 32-bit row offsets");
+  const int64_t dim = idx.dim;
+  const size_t esz  = elem_size(et);
+  dev_buf<int64_t> ids_dev;
+  if (new_ids && ids_on_host) {
+    ids_dev = dev_buf<int64_t>(res, n_new);
+    copy_async(res, ids_dev.data(), new_ids, n_new * sizeof(int64_t));
+    new_ids = ids_dev.data();
+  }
+  dev_buf<uint32_t> labels(res, n_new);
+  dev_buf<float> zero_norms(res, idx.n_lists);
+  hipLaunchKernelGGL(sq_zero_norms_kernel, dim3(grid_blocks(idx.n_lists, 256)), dim3(256), 0, res.stream, zero_norms.data(),
+                     (int)idx.n_lists);
+  const int64_t batch_rows = std::max<int64_t>(1024, std::min<int64_t>(n_new, (int64_t(1) << 28) / dim));
+  {
+    dev_buf<float> xb(res, (size_t)std::min(batch_rows, n_new) * dim);
+    for (int64_t r0 = 0; r0 < n_new; r0 += batch_rows) {
+      const int64_t cnt = std::min(batch_rows, n_new - r0);
+      load_range_as_float(res, data, et, is_host, dim, r0, cnt, xb.data());
+      sq_predict(res, idx, xb.data(), cnt, zero_norms.data(), labels.data() + r0);
+    }
+  }
+  // rows appended to their lists in input order: perm = rows ordered by (label, row)
+  dev_buf<uint32_t> perm(res, n_new), new_off(res, idx.n_lists + 1);
+  group_by_label(res, labels.data(), n_new, idx.n_lists, perm.data(), new_off.data());
+  std::vector<uint32_t> h_new_off = to_host(res, new_off.data(), idx.n_lists + 1);
+  std::vector<uint32_t> sizes(idx.n_lists), offs(idx.n_lists + 1);
+  int64_t total = 0;
+  for (uint32_t L = 0; L < idx.n_lists; ++L) {
+    sizes[L] = idx.h_list_sizes[L] + (h_new_off[L + 1] - h_new_off[L]);
+    offs[L]  = (uint32_t)total;
+    total += round_up(sizes[L], 64);
+  }
+  offs[idx.n_lists] = (uint32_t)total;
+  auto ndata    = dev_buf<uint8_t>::persistent((size_t)total * idx.n_chunks * 16);
+  auto nindices = dev_buf<int64_t>::persistent((size_t)total);
+  HIP_TRY(hipMemsetAsync(ndata.data(), 0, ndata.bytes(), res.stream));
+  HIP_TRY(hipMemsetAsync(nindices.data(), 0xff, nindices.bytes(), res.stream));
+  dev_buf<uint32_t> d_list_off(res, idx.n_lists + 1);
+  copy_async(res, d_list_off.data(), offs.data(), offs.size() * sizeof(uint32_t));
+  if (idx.size > 0)
+    hipLaunchKernelGGL(sq_relocate_lists_kernel, dim3(idx.n_lists), dim3(256), 0, res.stream, idx.data.data(), idx.indices.data(),
+                       idx.list_offsets.data(), idx.list_sizes.data(), d_list_off.data(), idx.n_chunks, ndata.data(), nindices.data());
+  sq_pack_args a;
+  a.perm = perm.data(); a.labels = labels.data(); a.new_off = new_off.data(); a.old_sizes = idx.list_sizes.data();
+  a.list_off = d_list_off.data(); a.new_ids = new_ids; a.id_base = idx.size;
+  a.centers = idx.centers.data(); a.vmin = idx.vmin.data(); a.delta = idx.delta.data();
+  a.dim = idx.dim; a.n_chunks = idx.n_chunks; a.data = ndata.data(); a.indices = nindices.data();
+  auto launch = [&](const sq_pack_args& pa) {
+    const int64_t work = pa.batch * pa.n_chunks;
+    if (et == elem_t::f32) hipLaunchKernelGGL(sq_pack_kernel<float>, dim3(grid_blocks(work, 256)), dim3(256), 0, res.stream, pa);
+    else                   hipLaunchKernelGGL(sq_pack_kernel<__half>, dim3(grid_blocks(work, 256)), dim3(256), 0, res.stream, pa);
+  };
+  const int64_t pb = int64_t(1) << 22;  // rows per pack launch
+  if (!is_host) {
+    a.src = data; a.src_is_batch = 0;
+    for (int64_t j0 = 0; j0 < n_new; j0 += pb) {
+      a.j0 = j0; a.batch = std::min(pb, n_new - j0);
+      launch(a);
+    }
+  } else {
+    std::vector<uint32_t> h_perm = to_host(res, perm.data(), n_new);
+    const int64_t hb = std::max<int64_t>(1, std::min<int64_t>(n_new, (int64_t(1) << 28) / (dim * (int64_t)esz)));
+    std::vector<char> host((size_t)hb * dim * esz);
+    dev_buf<char> stage(res, host.size());
+    const char* src = static_cast<const char*>(data);
+    for (int64_t j0 = 0; j0 < n_new; j0 += hb) {
+      const int64_t cnt = std::min(hb, n_new - j0);
+      for (int64_t i = 0; i < cnt; ++i)
+        memcpy(host.data() + (size_t)i * dim * esz, src + (size_t)h_perm[j0 + i] * dim * esz, dim * esz);
+      copy_async(res, stage.data(), host.data(), (size_t)cnt * dim * esz);
+      a.src = stage.data(); a.src_is_batch = 1; a.j0 = j0; a.batch = cnt;
+      launch(a);
+      sync(res);
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  sync(res);
+  idx.data    = std::move(ndata);
+  idx.indices = std::move(nindices);
+  copy_async(res, idx.list_sizes.data(), sizes.data(), sizes.size() * sizeof(uint32_t));
+  copy_async(res, idx.list_offsets.data(), offs.data(), offs.size() * sizeof(uint32_t));
+  sq_set_center_norms(res, idx);
+  sync(res);
+  idx.h_list_sizes   = sizes;
+  idx.h_list_offsets = offs;
+  idx.size += n_new;
+  idx.padded_rows = total;
+}
+
+std::unique_ptr<ivf_sq_index> ivf_sq_build(resources& res, const cuvsIvfSqIndexParams& p, const void* data, elem_t et,
+                                           int64_t n, int64_t dim, bool is_host)
+{
+  CUVS_EXPECTS(et == elem_t::f32 || et == elem_t::f16, "ivf_sq::build: dataset must be float32 or float16");
+  CUVS_EXPECTS(n > 0 && dim > 0, "empty dataset");
+  CUVS_EXPECTS(p.n_lists > 0 && n >= p.n_lists, "number of rows can't be less than n_lists");
+  CUVS_EXPECTS(p.max_train_points_per_cluster > 0, "max_train_points_per_cluster must be > 0");
+  const int metric = (int)p.metric;
+  CUVS_EXPECTS(sq_metric_ok(metric), "ivf_sq: unsupported metric %d (L2Expanded, L2SqrtExpanded, InnerProduct, CosineExpanded)",
+               metric);
+  CUVS_EXPECTS(metric != M_CosineExpanded || dim > 1, "Cosine metric requires more than one dim");
+  CUVS_EXPECTS(dim < (int64_t(1) << 24), "ivf_sq: dim too large");
+  auto idx   = sq_empty_index(res, metric, p.n_lists, (uint32_t)dim, p.conservative_memory_allocation);
+  idx->dtype = et;
+  // training sample: min(n, n_lists * max_train_points_per_cluster) distinct rows, chosen by a seeded shuffle (all rows
+  // when the dataset is no larger), gathered in ascending row order
+  const int64_t n_train = std::min<int64_t>(n, (int64_t)p.n_lists * p.max_train_points_per_cluster);
+  std::vector<uint32_t> pick((size_t)n);
+  std::iota(pick.begin(), pick.end(), 0u);
+  if (n_train < n) {
+    std::mt19937_64 rng(137);
+    for (int64_t i = 0; i < n_train; ++i) {
+      const int64_t j = i + (int64_t)(rng() % (uint64_t)(n - i));
+      std::swap(pick[i], pick[j]);
+    }
+    pick.resize((size_t)n_train);
+    std::sort(pick.begin(), pick.end());
+  }
+  dev_buf<float> trainset(res, (size_t)n_train * dim);
+  {
+    dev_buf<uint32_t> ids(res, n_train);
+    copy_async(res, ids.data(), pick.data(), (size_t)n_train * sizeof(uint32_t));
+    load_gather_as_float(res, data, et, is_host, dim, ids.data(), n_train, trainset.data());
+    sync(res);
+  }
+  {
+    // k-means on the sample (cosine: on unit-length copies), then the sample's labels with the index metric
+    dev_buf<float> fit(res, (size_t)n_train * dim);
+    HIP_TRY(hipMemcpyAsync(fit.data(), trainset.data(), trainset.bytes(), hipMemcpyDeviceToDevice, res.stream));
+    if (metric == M_CosineExpanded) normalize_rows(res, fit.data(), n_train, dim);
+    kmeans_params kp;
+    kp.n_iters       = (int)p.kmeans_n_iters;
+    kp.inner_product = metric == M_InnerProduct;
+    kmeans_balanced_fit(res, fit.data(), n_train, dim, (int)p.n_lists, kp, idx->centers.data());
+    sq_set_center_norms(res, *idx);
+    HIP_TRY(hipMemcpyAsync(fit.data(), trainset.data(), trainset.bytes(), hipMemcpyDeviceToDevice, res.stream));
+    dev_buf<uint32_t> labels(res, n_train);
+    dev_buf<float> zero_norms(res, p.n_lists);
+    hipLaunchKernelGGL(sq_zero_norms_kernel, dim3(grid_blocks(p.n_lists, 256)), dim3(256), 0, res.stream, zero_norms.data(),
+                       (int)p.n_lists);
+    sq_predict(res, *idx, fit.data(), n_train, zero_norms.data(), labels.data());
+    // residuals -> per-dimension range -> quantizer
+    hipLaunchKernelGGL(sq_residuals_kernel, dim3(grid_blocks(n_train * dim, 256)), dim3(256), 0, res.stream, trainset.data(),
+                       idx->centers.data(), labels.data(), n_train, (uint32_t)dim, et == elem_t::f16 ? 1 : 0);
+    dev_buf<float> pmin(res, (size_t)kMinMaxBlocks * dim), pmax(res, (size_t)kMinMaxBlocks * dim);
+    hipLaunchKernelGGL(sq_minmax_partial_kernel, dim3(kMinMaxBlocks), dim3(256), 0, res.stream, trainset.data(), n_train,
+                       (uint32_t)dim, pmin.data(), pmax.data());
+    hipLaunchKernelGGL(sq_quantizer_kernel, dim3(grid_blocks(dim, 256)), dim3(256), 0, res.stream, pmin.data(), pmax.data(),
+                       kMinMaxBlocks, (uint32_t)dim, idx->vmin.data(), idx->delta.data());
+    HIP_TRY(hipGetLastError());
+    sync(res);
+  }
+  trainset.release();
+  if (p.add_data_on_build) ivf_sq_extend(res, *idx, data, et, n, is_host, nullptr, false);
+  sync(res);
+  return idx;
+}
+
+void ivf_sq_search(resources& res, const ivf_sq_index& idx, uint32_t n_probes_in, const void* queries, elem_t et,
+                   int64_t n_queries, int k, int64_t* neighbors, float* distances, const uint32_t* filter_bits)
+{
+  CUVS_EXPECTS(k > 0, "ivf_sq::search: k must be positive");
+  CUVS_EXPECTS(n_probes_in > 0, "n_probes must be positive");
+  CUVS_EXPECTS(et == elem_t::f32 || et == elem_t::f16, "ivf_sq::search: queries must be float32 or float16");
+  if (n_queries == 0) return;
+  const uint32_t n_probes = std::min<uint32_t>(n_probes_in, idx.n_lists);
+  const int qpb           = kSqQPB;
+  const bool large_k      = k > 256;  // beyond the register top lists: every score written, then select_k
+  const bool big_k        = k > 64 && !large_k;
+  const int k_scan        = large_k ? 1 : k;
+  const uint32_t dim_pad  = idx.n_chunks * 16;
+  const int metric_kind   = idx.metric == M_InnerProduct ? 1 : idx.metric == M_CosineExpanded ? 2 : 0;
+  const bool ipm = idx.metric == M_InnerProduct, cosm = idx.metric == M_CosineExpanded;
+  const size_t smem      = ((((size_t)qpb * kSqWaves * k_scan * 8) + 15) & ~size_t(15)) + 2 * 16 * 4;
+  const size_t scores_ld = large_k ? largest_lists_total(idx.h_list_sizes, n_probes) : 0;
+  int64_t max_batch = 1 << 15;
+  {
+    int64_t per_q = (int64_t)idx.n_lists * 4 + (int64_t)n_probes * k_scan * 8 + idx.dim * 4 +
+                    ((int64_t)n_probes / qpb + 1) * (dim_pad + 1) * qpb * 4;
+    if (large_k) per_q += (int64_t)scores_ld * 8 + (int64_t)k * 12;
+    per_q += round_up((int64_t)idx.n_lists, 128) * 4 + round_up((int64_t)idx.n_lists, 128) / 4;
+    max_batch = balanced_batch(n_queries, std::min(max_batch, std::max<int64_t>(1, (int64_t)res.ivf_batch_limit / per_q)));
+  }
+  const int64_t bs     = std::min<int64_t>(max_batch, n_queries);
+  const int64_t np_max = bs * n_probes;
+  // two-phase schedule (ivf_common.hpp): the nearest probe of every query first leaves tight bounds for the L2 early stop
+  const uint32_t head     = (n_probes > 8 && metric_kind == 0 && !large_k) ? 1u : 0u;
+  const uint32_t n_labels = head > 0 ? 2 * idx.n_lists : idx.n_lists;
+  dev_buf<float> qf(res, (size_t)bs * idx.dim), qn(res, bs), pd(res, (size_t)np_max);
+  dev_buf<float> dist;
+  dev_buf<uint32_t> probes(res, np_max), sorted_pairs(res, np_max), pair_off(res, n_labels + 1), item_off(res, n_labels + 1),
+    cand_i(res, large_k ? (size_t)bs * scores_ld : (size_t)np_max * k), top_i(res, (size_t)bs * k), query_kth(res, bs),
+    pair_seg(res, large_k ? (size_t)np_max : 0), phase_labels(res, head > 0 ? (size_t)np_max : 0);
+  const size_t max_items = (size_t)(np_max / qpb + n_labels + 1);
+  dev_buf<work_item> items(res, max_items);
+  dev_buf<float> qtiles(res, max_items * (dim_pad + 1) * qpb);
+  dev_buf<float> cand_d(res, large_k ? (size_t)bs * scores_ld : (size_t)np_max * k), top_d(res, (size_t)bs * k);
+  dev_buf<float> delta_pad(res, dim_pad), aux(res, metric_kind != 0 ? (size_t)idx.n_lists * dim_pad : 0);
+  hipLaunchKernelGGL(sq_search_terms_kernel, dim3(grid_blocks(std::max<int64_t>(dim_pad, (int64_t)idx.n_lists * dim_pad), 256)),
+                     dim3(256), 0, res.stream, idx.centers.data(), idx.vmin.data(), idx.delta.data(), idx.n_lists, idx.dim,
+                     dim_pad, metric_kind != 0 ? 1 : 0, delta_pad.data(), aux.data());
+  const size_t esz = elem_size(et);
+
+  for (int64_t q0 = 0; q0 < n_queries; q0 += max_batch) {
+    const int64_t nq      = std::min(max_batch, n_queries - q0);
+    const int64_t n_pairs = nq * n_probes;
+    load_range_as_float(res, queries, et, false, idx.dim, q0, nq, qf.data());
+    (void)esz;
+    // coarse search: the calls and tie rule of ivf_flat_search
+    bool coarse_done = false;
+    if (res.tune.coarse_grouped != 0 && select_k_grouped_ok(idx.n_lists, (int)n_probes)) {
+      const int64_t ldo = round_up((int64_t)idx.n_lists, 128);
+      dev_buf<float> gdist(res, (size_t)nq * ldo);
+      dev_buf<uint32_t> gkeys(res, (size_t)nq * (ldo / 16));
+      if (!ipm) row_norms<float>(res, qf.data(), nq, idx.dim, idx.dim, qn.data(), cosm);
+      coarse_done = pairwise_distance_grouped(res, qf.data(), nq, idx.dim, idx.centers.data(), idx.n_lists, idx.dim, idx.dim,
+                                              ipm ? nullptr : qn.data(), ipm ? nullptr : (cosm ? idx.center_norms_sqrt.data() : idx.center_norms.data()),
+                                              ipm ? (int)M_InnerProduct : (cosm ? (int)M_CosineExpanded : (int)M_L2Expanded), gdist.data(), ldo,
+                                              gkeys.data(), ldo / 16);
+      if (coarse_done)
+        select_k_grouped(res, gdist.data(), ldo, gkeys.data(), ldo / 16, nq, idx.n_lists, (int)n_probes, pd.data(), probes.data(), !ipm);
+    }
+    if (!coarse_done && dist.data() == nullptr) dist = dev_buf<float>(res, (size_t)bs * idx.n_lists);
+    if (coarse_done) {
+    } else if (ipm) {
+      pairwise_distance<float, float>(res, qf.data(), nq, idx.dim, idx.centers.data(), idx.n_lists, idx.dim, idx.dim, nullptr,
+                                      nullptr, M_InnerProduct, dist.data(), idx.n_lists);
+      select_k<uint32_t, uint32_t>(res, dist.data(), nullptr, nq, idx.n_lists, idx.n_lists, (int)n_probes, pd.data(),
+                                   probes.data(), false);
+    } else if (cosm) {
+      row_norms<float>(res, qf.data(), nq, idx.dim, idx.dim, qn.data(), true);
+      pairwise_distance<float, float>(res, qf.data(), nq, idx.dim, idx.centers.data(), idx.n_lists, idx.dim, idx.dim, qn.data(),
+                                      idx.center_norms_sqrt.data(), M_CosineExpanded, dist.data(), idx.n_lists);
+      select_k<uint32_t, uint32_t>(res, dist.data(), nullptr, nq, idx.n_lists, idx.n_lists, (int)n_probes, pd.data(),
+                                   probes.data(), true);
+    } else {
+      row_norms<float>(res, qf.data(), nq, idx.dim, idx.dim, qn.data(), false);
+      pairwise_distance<float, float>(res, qf.data(), nq, idx.dim, idx.centers.data(), idx.n_lists, idx.dim, idx.dim, qn.data(),
+                                      idx.center_norms.data(), M_L2Expanded, dist.data(), idx.n_lists);
+      select_k<uint32_t, uint32_t>(res, dist.data(), nullptr, nq, idx.n_lists, idx.n_lists, (int)n_probes, pd.data(),
+                                   probes.data(), true);
+    }
+    const uint32_t* labels = probes.data();
+    if (head > 0) {
+      hipLaunchKernelGGL(phase_labels_kernel, dim3(grid_blocks(n_pairs, 256)), dim3(256), 0, res.stream, probes.data(), n_pairs,
+                         n_probes, head, idx.n_lists, phase_labels.data());
+      labels = phase_labels.data();
+    }
+    build_work_items(res, labels, n_pairs, n_labels, qpb, sorted_pairs.data(), pair_off.data(), item_off.data(), items.data());
+    HIP_TRY(hipMemsetAsync(query_kth.data(), 0xff, (size_t)nq * sizeof(uint32_t), res.stream));
+    if (large_k) {
+      HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(cand_d.data()), 0x7f7fffff, (size_t)nq * scores_ld, res.stream));
+      HIP_TRY(hipMemsetAsync(cand_i.data(), 0xff, (size_t)nq * scores_ld * sizeof(uint32_t), res.stream));
+      hipLaunchKernelGGL(pair_segments_kernel, dim3(grid_blocks(nq, 256)), dim3(256), 0, res.stream, probes.data(),
+                         idx.list_sizes.data(), nq, n_probes, pair_seg.data());
+    }
+    // (cosine: qn holds |q| from the coarse search's row_norms)
+    hipLaunchKernelGGL(sq_query_tiles_kernel, dim3((unsigned)(n_pairs / qpb + n_labels + 1)), dim3(256), 0, res.stream,
+                       items.data(), item_off.data() + n_labels, sorted_pairs.data(), qf.data(), cosm ? qn.data() : nullptr,
+                       idx.centers.data(), idx.vmin.data(), n_probes, idx.n_lists, idx.dim, dim_pad, metric_kind == 0 ? 1 : 0,
+                       qtiles.data());
+    sq_scan_args a{};
+    a.items = items.data(); a.n_lists = idx.n_lists; a.sorted_pairs = sorted_pairs.data(); a.qtiles = qtiles.data();
+    a.delta_pad = delta_pad.data(); a.aux = aux.data(); a.data = idx.data.data(); a.list_offsets = idx.list_offsets.data();
+    a.list_sizes = idx.list_sizes.data(); a.out_d = cand_d.data(); a.out_i = cand_i.data(); a.query_kth = query_kth.data();
+    a.filter_bits = filter_bits; a.indices = idx.indices.data(); a.n_probes = n_probes; a.n_chunks = idx.n_chunks;
+    a.k = (uint32_t)k_scan; a.all_scores = large_k ? cand_d.data() : nullptr; a.all_rows = cand_i.data();
+    a.pair_seg = pair_seg.data(); a.scores_ld = scores_ld;
+    // grids are upper bounds of the (device-side) item counts of each phase; surplus workgroups exit at once
+    if (head > 0) {
+      a.item_begin = nullptr; a.item_end = item_off.data() + idx.n_lists;
+      launch_sq_scan(res, a, metric_kind, smem, (unsigned)(nq * head / qpb + idx.n_lists + 1), big_k);
+      a.item_begin = item_off.data() + idx.n_lists; a.item_end = item_off.data() + 2 * idx.n_lists;
+      launch_sq_scan(res, a, metric_kind, smem, (unsigned)(nq * (n_probes - head) / qpb + idx.n_lists + 1), big_k);
+    } else {
+      a.item_begin = nullptr; a.item_end = item_off.data() + idx.n_lists;
+      launch_sq_scan(res, a, metric_kind, smem, (unsigned)(n_pairs / qpb + idx.n_lists + 1), big_k);
+    }
+    if (!large_k)
+      select_k<uint32_t, uint32_t>(res, cand_d.data(), cand_i.data(), nq, (int64_t)n_probes * k, (int64_t)n_probes * k, k,
+                                   top_d.data(), top_i.data(), true);
+    else
+      select_k<uint32_t, uint32_t>(res, cand_d.data(), cand_i.data(), nq, (int64_t)scores_ld, (int64_t)scores_ld, k, top_d.data(),
+                                   top_i.data(), true);
+    hipLaunchKernelGGL(sq_postprocess_kernel, dim3(grid_blocks(nq * k, 256)), dim3(256), 0, res.stream, top_i.data(), top_d.data(),
+                       nq * k, idx.indices.data(), idx.metric, neighbors + q0 * k, distances + q0 * k);
+  }
+  HIP_TRY(hipGetLastError());
+}
+
+}  // namespace cuvs_amd
+
+using namespace cuvs_amd;
+
+namespace {
+ivf_sq_index& get_sq(cuvsIvfSqIndex_t index)
+{
+  CUVS_EXPECTS(index != nullptr && index->addr != 0, "IVF-SQ index is not built");
+  return *reinterpret_cast<ivf_sq_index*>(index->addr);
+}
+
+const uint32_t* sq_filter_bits(const cuvsFilter& filter)
+{
+  if (filter.type == NO_FILTER) return nullptr;
+  CUVS_EXPECTS(filter.type == BITSET, "Unsupported filter type: BITMAP");
+  CUVS_EXPECTS(filter.addr != 0, "filter tensor is null");
+  auto& ft = reinterpret_cast<DLManagedTensor*>(filter.addr)->dl_tensor;
+  CUVS_EXPECTS(dtype_is(ft.dtype, kDLUInt, 32) && is_device_accessible(ft), "filter must be a device uint32 tensor");
+  return static_cast<const uint32_t*>(dl_data(ft));
+}
+
+bool sq_input_dtype_ok(const DLDataType& d) { return d.code == kDLFloat && (d.bits == 32 || d.bits == 16); }
+}  // namespace
+
+extern "C" {
+
+cuvsError_t cuvsIvfSqIndexParamsCreate(cuvsIvfSqIndexParams_t* params)
+{
+  return (cuvsError_t)translate_exceptions(
+    [=] { *params = new cuvsIvfSqIndexParams{L2Expanded, 2.0f, true, 1024, 20, 256, false}; });
+}
+cuvsError_t cuvsIvfSqIndexParamsDestroy(cuvsIvfSqIndexParams_t params)
+{
+  return (cuvsError_t)translate_exceptions([=] { delete params; });
+}
+cuvsError_t cuvsIvfSqSearchParamsCreate(cuvsIvfSqSearchParams_t* params)
+{
+  return (cuvsError_t)translate_exceptions([=] { *params = new cuvsIvfSqSearchParams{20}; });
+}
+cuvsError_t cuvsIvfSqSearchParamsDestroy(cuvsIvfSqSearchParams_t params)
+{
+  return (cuvsError_t)translate_exceptions([=] { delete params; });
+}
+cuvsError_t cuvsIvfSqIndexCreate(cuvsIvfSqIndex_t* index)
+{
+  return (cuvsError_t)translate_exceptions([=] { *index = new cuvsIvfSqIndex{0, DLDataType{0, 0, 0}}; });
+}
+cuvsError_t cuvsIvfSqIndexDestroy(cuvsIvfSqIndex_t index)
+{
+  return (cuvsError_t)translate_exceptions([=] {
+    if (!index) return;
+    delete reinterpret_cast<ivf_sq_index*>(index->addr);
+    delete index;
+  });
+}
+cuvsError_t cuvsIvfSqIndexGetNLists(cuvsIvfSqIndex_t index, int64_t* n_lists)
+{
+  return (cuvsError_t)translate_exceptions([=] { *n_lists = get_sq(index).n_lists; });
+}
+cuvsError_t cuvsIvfSqIndexGetDim(cuvsIvfSqIndex_t index, int64_t* dim)
+{
+  return (cuvsError_t)translate_exceptions([=] { *dim = get_sq(index).dim; });
+}
+cuvsError_t cuvsIvfSqIndexGetSize(cuvsIvfSqIndex_t index, int64_t* size)
+{
+  return (cuvsError_t)translate_exceptions([=] { *size = get_sq(index).size; });
+}
+cuvsError_t cuvsIvfSqIndexGetCenters(cuvsIvfSqIndex_t index, DLManagedTensor* centers)
+{
+  return (cuvsError_t)translate_exceptions([=] {
+    auto& idx = get_sq(index);
+    fill_dl_view(centers, idx.centers.data(), DLDataType{kDLFloat, 32, 1}, idx.n_lists, idx.dim, 2, 0);
+  });
+}
+
+cuvsError_t cuvsIvfSqBuild(cuvsResources_t res_h, cuvsIvfSqIndexParams_t params, DLManagedTensor* dataset_tensor,
+                           cuvsIvfSqIndex_t index)
+{
+  return (cuvsError_t)translate_exceptions([=] {
+    auto& res = *as_res(res_h);
+    CUVS_EXPECTS(params && dataset_tensor && index, "null argument");
+    auto& ds = dataset_tensor->dl_tensor;
+    CUVS_EXPECTS(sq_input_dtype_ok(ds.dtype), "Unsupported dataset DLtensor dtype: %d and bits: %d", (int)ds.dtype.code,
+                 (int)ds.dtype.bits);
+    CUVS_EXPECTS(ds.ndim == 2 && is_c_contiguous(ds), "dataset must be a row-major matrix");
+    auto idx = ivf_sq_build(res, *params, dl_data(ds), elem_of(ds.dtype), ds.shape[0], ds.shape[1], !is_device_accessible(ds));
+    delete reinterpret_cast<ivf_sq_index*>(index->addr);
+    index->addr  = reinterpret_cast<uintptr_t>(idx.release());
+    index->dtype = DLDataType{ds.dtype.code, ds.dtype.bits, 1};
+  });
+}
+
+cuvsError_t cuvsIvfSqSearch(cuvsResources_t res_h, cuvsIvfSqSearchParams_t params, cuvsIvfSqIndex_t index_c,
+                            DLManagedTensor* queries_tensor, DLManagedTensor* neighbors_tensor,
+                            DLManagedTensor* distances_tensor, cuvsFilter filter)
+{
+  return (cuvsError_t)translate_exceptions([=] {
+    auto& res = *as_res(res_h);
+    auto& idx = get_sq(index_c);
+    CUVS_EXPECTS(params && queries_tensor && neighbors_tensor && distances_tensor, "null argument");
+    const uint32_t* bits = sq_filter_bits(filter);
+    auto& queries   = queries_tensor->dl_tensor;
+    auto& neighbors = neighbors_tensor->dl_tensor;
+    auto& distances = distances_tensor->dl_tensor;
+    CUVS_EXPECTS(is_device_accessible(queries), "queries should have device compatible memory");
+    CUVS_EXPECTS(is_device_accessible(neighbors), "neighbors should have device compatible memory");
+    CUVS_EXPECTS(is_device_accessible(distances), "distances should have device compatible memory");
+    CUVS_EXPECTS(dtype_is(neighbors.dtype, kDLInt, 64), "neighbors should be of type int64_t");
+    CUVS_EXPECTS(dtype_is(distances.dtype, kDLFloat, 32), "distances should be of type float32");
+    CUVS_EXPECTS(sq_input_dtype_ok(queries.dtype), "Unsupported queries DLtensor dtype: %d and bits: %d",
+                 (int)queries.dtype.code, (int)queries.dtype.bits);
+    CUVS_EXPECTS(queries.ndim == 2 && neighbors.ndim == 2 && distances.ndim == 2, "tensors must be 2-D");
+    CUVS_EXPECTS(is_c_contiguous(queries) && is_c_contiguous(neighbors) && is_c_contiguous(distances),
+                 "tensors must be C-contiguous");
+    CUVS_EXPECTS(queries.shape[1] == idx.dim, "queries dim %ld != index dim %u", (long)queries.shape[1], idx.dim);
+    const int64_t m = queries.shape[0], k = neighbors.shape[1];
+    CUVS_EXPECTS(neighbors.shape[0] == m && distances.shape[0] == m && distances.shape[1] == k,
+                 "neighbors/distances shape mismatch");
+    ivf_sq_search(res, idx, params->n_probes, dl_data(queries), elem_of(queries.dtype), m, (int)k,
+                  static_cast<int64_t*>(dl_data(neighbors)), static_cast<float*>(dl_data(distances)), bits);
+  });
+}
+
+cuvsError_t cuvsIvfSqExtend(cuvsResources_t res_h, DLManagedTensor* new_vectors, DLManagedTensor* new_indices,
+                            cuvsIvfSqIndex_t index_c)
+{
+  return (cuvsError_t)translate_exceptions([=] {
+    auto& res = *as_res(res_h);
+    auto& idx = get_sq(index_c);
+    CUVS_EXPECTS(new_vectors != nullptr, "new_vectors is null");
+    auto& v = new_vectors->dl_tensor;
+    CUVS_EXPECTS(sq_input_dtype_ok(v.dtype), "Unsupported vectors DLtensor dtype: %d and bits: %d", (int)v.dtype.code,
+                 (int)v.dtype.bits);
+    CUVS_EXPECTS(v.ndim == 2 && is_c_contiguous(v) && v.shape[1] == idx.dim, "new_vectors must be [n, dim] row-major");
+    const bool on_device = is_device_accessible(v);
+    const int64_t* ids   = nullptr;
+    bool ids_host        = false;
+    if (new_indices != nullptr) {
+      auto& t = new_indices->dl_tensor;
+      CUVS_EXPECTS(dtype_is(t.dtype, kDLInt, 64) && t.ndim == 1 && t.shape[0] == v.shape[0], "new_indices must be int64 [n]");
+      CUVS_EXPECTS(is_device_accessible(t) == on_device, "extend inputs must both either be on device memory or host memory");
+      ids      = static_cast<const int64_t*>(dl_data(t));
+      ids_host = !is_device_accessible(t);
+    }
+    if (index_c->dtype.code == 0 && index_c->dtype.bits == 0) index_c->dtype = DLDataType{v.dtype.code, v.dtype.bits, 1};
+    ivf_sq_extend(res, idx, dl_data(v), elem_of(v.dtype), v.shape[0], !on_device, ids, ids_host);
+  });
+}
+
+}  // extern "C"
+
+namespace {
+constexpr int kSqRefVersion = 1;  // ivf_sq_serialize.cuh
+
+// the reference's list record interleave (ivf_sq.hpp: kIndexGroupSize 32, kVecLen 16): byte offset of (row r, dim d) in a
+// list record [rows32, dim_pad]
+inline size_t ref_sq_offset(uint32_t r, uint32_t d, uint32_t dim_pad)
+{
+  return (size_t)(r / 32) * 32 * dim_pad + (size_t)(d / 16) * 32 * 16 + (size_t)(r % 32) * 16 + d % 16;
+}
+
+// Record sequence: dtype prefix "|u1", version, size, dim, n_lists, metric, conservative_memory_allocation, centers,
+// has_norms [, center norms], vmin, delta, list_sizes, then per list: rows32 = roundUp(size, 32) [, codes [rows32, dim_pad]
+// in the reference's 32-row interleave, ids [rows32]]. Our lists are stored in 64-row tiles: re-interleaved on the host.
+void sq_write_ref(resources& res, const char* filename, const ivf_sq_index& idx)
+{
+  npy_writer w(filename);
+  char prefix[4];
+  elem_prefix(elem_t::u8, prefix);
+  w.raw(prefix, 4);
+  w.scalar<int32_t>(kSqRefVersion);
+  w.scalar<int64_t>(idx.size);
+  w.scalar<uint32_t>(idx.dim);
+  w.scalar<uint32_t>(idx.n_lists);
+  w.scalar<int32_t>(idx.metric);
+  w.scalar<bool>(idx.conservative_memory_allocation);
+  w.device_array(res, 'f', 4, {idx.n_lists, idx.dim}, idx.centers.data());
+  const bool has_norms = idx.metric != M_InnerProduct;
+  w.scalar<bool>(has_norms);
+  if (has_norms)
+    w.device_array(res, 'f', 4, {idx.n_lists}, idx.metric == M_CosineExpanded ? idx.center_norms_sqrt.data() : idx.center_norms.data());
+  w.device_array(res, 'f', 4, {idx.dim}, idx.vmin.data());
+  w.device_array(res, 'f', 4, {idx.dim}, idx.delta.data());
+  w.host_array<uint32_t>(idx.h_list_sizes.data(), {idx.n_lists});
+  const uint32_t dim_pad = idx.n_chunks * 16;
+  std::vector<uint8_t> ours, theirs;
+  std::vector<int64_t> ids;
+  for (uint32_t L = 0; L < idx.n_lists; ++L) {
+    const uint32_t size = idx.h_list_sizes[L], rows32 = (uint32_t)round_up(size, 32);
+    w.scalar<uint32_t>(rows32);
+    if (rows32 == 0) continue;
+    const uint32_t cap = idx.h_list_offsets[L + 1] - idx.h_list_offsets[L];
+    ours.resize((size_t)cap * idx.n_chunks * 16);
+    ids.assign(rows32, -1);
+    copy_async(res, ours.data(), idx.data.data() + (size_t)idx.h_list_offsets[L] * idx.n_chunks * 16, ours.size());
+    copy_async(res, ids.data(), idx.indices.data() + idx.h_list_offsets[L], (size_t)size * sizeof(int64_t));
+    sync(res);
+    theirs.assign((size_t)rows32 * dim_pad, 0);
+    for (uint32_t r = 0; r < size; ++r) {
+      const uint8_t* row = ours.data() + ((size_t)(r / 64) * idx.n_chunks * 64 + r % 64) * 16;
+      for (uint32_t ch = 0; ch < idx.n_chunks; ++ch)
+        memcpy(theirs.data() + ref_sq_offset(r, ch * 16, dim_pad), row + (size_t)ch * 64 * 16, 16);
+    }
+    w.header('u', 1, {rows32, dim_pad});
+    w.raw(theirs.data(), theirs.size());
+    w.host_array<int64_t>(ids.data(), {rows32});
+  }
+  w.close();
+}
+
+std::unique_ptr<ivf_sq_index> sq_read_ref(resources& res, const char* filename)
+{
+  npy_reader r(filename);
+  char prefix[4];
+  r.raw(prefix, 4);
+  elem_t code_t;
+  CUVS_EXPECTS(parse_elem_prefix(prefix, &code_t) && code_t == elem_t::u8,
+               "ivf_sq::deserialize: serialized dtype prefix does not match requested type");
+  const int ver = r.scalar<int32_t>();
+  CUVS_EXPECTS(ver == kSqRefVersion, "serialization version mismatch, expected %d, got %d ", kSqRefVersion, ver);
+  const int64_t size     = r.scalar<int64_t>();
+  const uint32_t dim     = r.scalar<uint32_t>();
+  const uint32_t n_lists = r.scalar<uint32_t>();
+  const int metric       = r.scalar<int32_t>();
+  const bool cma         = r.scalar<bool>();
+  CUVS_EXPECTS(sq_metric_ok(metric), "ivf_sq::deserialize: invalid metric value %d", metric);
+  CUVS_EXPECTS(n_lists <= (1u << 24), "ivf_sq::deserialize: n_lists=%u exceeds maximum %u", n_lists, 1u << 24);
+  CUVS_EXPECTS(dim > 0 && n_lists > 0 && dim < (1u << 24), "ivf_sq::deserialize: bad header");
+  auto idx  = sq_empty_index(res, metric, n_lists, dim, cma);
+  idx->size = size;
+  idx->centers = r.device_array<float>(res, (int64_t)n_lists * dim);
+  if (r.scalar<bool>()) (void)r.host_array<float>(n_lists);
+  sq_set_center_norms(res, *idx);  // canonical norms (the build's own rounding) rather than the file's
+  idx->vmin  = r.device_array<float>(res, dim);
+  idx->delta = r.device_array<float>(res, dim);
+  idx->h_list_sizes = r.host_array<uint32_t>(n_lists);
+  int64_t total = 0, live = 0;
+  for (uint32_t L = 0; L < n_lists; ++L) {
+    idx->h_list_offsets[L] = (uint32_t)total;
+    total += round_up(idx->h_list_sizes[L], 64);
+    live += idx->h_list_sizes[L];
+  }
+  CUVS_EXPECTS(total < (int64_t(1) << 32), "ivf_sq::deserialize: index too large");
+  CUVS_EXPECTS(live == size, "ivf_sq::deserialize: list sizes (%ld) do not add up to the index size (%ld)", (long)live, (long)size);
+  idx->h_list_offsets[n_lists] = (uint32_t)total;
+  idx->padded_rows             = total;
+  copy_async(res, idx->list_sizes.data(), idx->h_list_sizes.data(), n_lists * sizeof(uint32_t));
+  copy_async(res, idx->list_offsets.data(), idx->h_list_offsets.data(), (n_lists + 1) * sizeof(uint32_t));
+  idx->data    = dev_buf<uint8_t>::persistent((size_t)total * idx->n_chunks * 16);
+  idx->indices = dev_buf<int64_t>::persistent((size_t)total);
+  HIP_TRY(hipMemsetAsync(idx->data.data(), 0, idx->data.bytes(), res.stream));
+  HIP_TRY(hipMemsetAsync(idx->indices.data(), 0xff, idx->indices.bytes(), res.stream));
+  sync(res);
+  const uint32_t dim_pad = idx->n_chunks * 16;
+  std::vector<uint8_t> ours;
+  std::vector<char> theirs;
+  for (uint32_t L = 0; L < n_lists; ++L) {
+    const uint32_t rows = r.scalar<uint32_t>(), sz = idx->h_list_sizes[L];
+    CUVS_EXPECTS(rows >= sz, "ivf_sq::deserialize: list %u holds %u rows, list_sizes says %u", L, rows, sz);
+    if (rows == 0) continue;
+    r.array(1, (int64_t)rows * dim_pad, theirs);
+    std::vector<int64_t> ids = r.host_array<int64_t>(rows);
+    if (sz == 0) continue;
+    ours.assign((size_t)round_up(sz, 64) * idx->n_chunks * 16, 0);
+    for (uint32_t rr = 0; rr < sz; ++rr) {
+      uint8_t* row = ours.data() + ((size_t)(rr / 64) * idx->n_chunks * 64 + rr % 64) * 16;
+      for (uint32_t ch = 0; ch < idx->n_chunks; ++ch)
+        memcpy(row + (size_t)ch * 64 * 16, theirs.data() + ref_sq_offset(rr, ch * 16, dim_pad), 16);
+    }
+    copy_async(res, idx->data.data() + (size_t)idx->h_list_offsets[L] * idx->n_chunks * 16, ours.data(), ours.size());
+    copy_async(res, idx->indices.data() + idx->h_list_offsets[L], ids.data(), (size_t)sz * sizeof(int64_t));
+    sync(res);
+  }
+  return idx;
+}
+}  // namespace
+
+extern "C" {
+cuvsError_t cuvsIvfSqSerialize(cuvsResources_t res_h, const char* filename, cuvsIvfSqIndex_t index)
+{
+  return (cuvsError_t)translate_exceptions([=] { sq_write_ref(*as_res(res_h), filename, get_sq(index)); });
+}
+cuvsError_t cuvsIvfSqDeserialize(cuvsResources_t res_h, const char* filename, cuvsIvfSqIndex_t index)
+{
+  return (cuvsError_t)translate_exceptions([=] {
+    auto& res = *as_res(res_h);
+    CUVS_EXPECTS(index != nullptr, "index is null");
+    auto idx = sq_read_ref(res, filename);
+    delete reinterpret_cast<ivf_sq_index*>(index->addr);
+    index->addr  = reinterpret_cast<uintptr_t>(idx.release());
+    index->dtype = DLDataType{0, 0, 0};
+  });
+}
+
+// test hooks (not in the reference ABI): list size; one list's codes row-major [size, dim] + source ids; the quantizer
+__attribute__((visibility("default"))) int cuvsAmdIvfSqListSize(cuvsIvfSqIndex_t index, uint32_t label, uint32_t* size)
+{
+  return translate_exceptions([=] {
+    auto& idx = get_sq(index);
+    CUVS_EXPECTS(label < idx.n_lists, "label out of range");
+    *size = idx.h_list_sizes[label];
+  });
+}
+
+__attribute__((visibility("default"))) int cuvsAmdIvfSqUnpackList(cuvsResources_t res_h, cuvsIvfSqIndex_t index, uint32_t label,
+                                                                   uint8_t* out_codes, int64_t* out_ids)
+{
+  return translate_exceptions([=] {
+    auto& res = *as_res(res_h);
+    auto& idx = get_sq(index);
+    CUVS_EXPECTS(label < idx.n_lists, "label out of range");
+    const uint32_t sz = idx.h_list_sizes[label];
+    if (sz == 0) return;
+    const int64_t total = (int64_t)sz * idx.dim;
+    hipLaunchKernelGGL(sq_unpack_list_kernel, dim3(grid_blocks(total, 256)), dim3(256), 0, res.stream, idx.data.data(), idx.n_chunks,
+                       idx.dim, (int64_t)idx.h_list_offsets[label], sz, out_codes);
+    copy_async(res, out_ids, idx.indices.data() + idx.h_list_offsets[label], (size_t)sz * sizeof(int64_t));
+    HIP_TRY(hipGetLastError());
+  });
+}
+
+// host copies of vmin [dim] and delta [dim]
+__attribute__((visibility("default"))) int cuvsAmdIvfSqGetQuantizer(cuvsResources_t res_h, cuvsIvfSqIndex_t index, float* vmin,
+                                                                     float* delta)
+{
+  return translate_exceptions([=] {
+    auto& res = *as_res(res_h);
+    auto& idx = get_sq(index);
+    copy_async(res, vmin, idx.vmin.data(), idx.vmin.bytes());
+    copy_async(res, delta, idx.delta.data(), idx.delta.bytes());
+    sync(res);
+  });
+}
+
+}  // extern "C"

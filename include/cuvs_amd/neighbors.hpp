@@ -192,6 +192,55 @@ void search(const resources& res, const search_params& p, const index<T>& idx, d
 }
 }  // namespace ivf_flat
 
+namespace ivf_sq {
+struct index_params {  // ivf_sq.hpp: 8-bit scalar-quantized IVF lists
+  cuvsDistanceType metric               = L2Expanded;
+  float metric_arg                      = 2.0f;
+  bool add_data_on_build                = true;
+  uint32_t n_lists                      = 1024;
+  uint32_t kmeans_n_iters               = 20;
+  uint32_t max_train_points_per_cluster = 256;
+  bool conservative_memory_allocation   = false;
+};
+struct search_params {
+  uint32_t n_probes = 20;
+};
+class index {  // codes are uint8 whatever the row type (float / half) the index was built from
+ public:
+  index() { check(cuvsIvfSqIndexCreate(&h_), "cuvsIvfSqIndexCreate"); }
+  ~index() { if (h_) cuvsIvfSqIndexDestroy(h_); }
+  index(index&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  index(const index&) = delete;
+  cuvsIvfSqIndex_t get() const { return h_; }
+
+ private:
+  cuvsIvfSqIndex_t h_ = nullptr;
+};
+template <typename T>
+index build(const resources& res, const index_params& p, device_matrix_view<const T> dataset)
+{
+  detail::c_params<cuvsIvfSqIndexParams_t, cuvsIvfSqIndexParamsCreate, cuvsIvfSqIndexParamsDestroy> cp;
+  *cp.p = cuvsIvfSqIndexParams{p.metric, p.metric_arg, p.add_data_on_build, p.n_lists, p.kmeans_n_iters,
+                               p.max_train_points_per_cluster, p.conservative_memory_allocation};
+  index idx;
+  detail::tensor<const T> d(dataset);
+  check(cuvsIvfSqBuild(res.get(), cp.p, d.get(), idx.get()), "cuvsIvfSqBuild");
+  return idx;
+}
+template <typename T>
+void search(const resources& res, const search_params& p, const index& idx, device_matrix_view<const T> queries,
+            device_matrix_view<int64_t> neighbors, device_matrix_view<float> distances)
+{
+  detail::c_params<cuvsIvfSqSearchParams_t, cuvsIvfSqSearchParamsCreate, cuvsIvfSqSearchParamsDestroy> cp;
+  cp.p->n_probes = p.n_probes;
+  detail::tensor<const T> q(queries);
+  detail::tensor<int64_t> n(neighbors);
+  detail::tensor<float> d(distances);
+  cuvsFilter none{0, NO_FILTER};
+  check(cuvsIvfSqSearch(res.get(), cp.p, idx.get(), q.get(), n.get(), d.get(), none), "cuvsIvfSqSearch");
+}
+}  // namespace ivf_sq
+
 namespace ivf_pq {
 enum class codebook_gen { PER_SUBSPACE = 0, PER_CLUSTER = 1 };
 struct index_params {  // ivf_pq.hpp:40-160
