@@ -30,8 +30,11 @@
 #include "pq_lut_math.hpp"
 #include "ivf_pq_scan3.hpp"
 
+#include <cuvs/neighbors/ivf_pq.h>
+
 #include <cfloat>
 #include <cstdlib>
+#include <functional>
 #include <mutex>
 #include <type_traits>
 
@@ -2054,6 +2057,561 @@ static void shard_exchange_stats(resources& res, const ivf_pq_index& idx)
   idx.shard_stats_valid = true;
 }
 
+namespace {
+
+// ------------------------------------------------------------------ the search plan
+// Which kernels a search runs and how large its scratch is, decided once on the host from the index's shape, the search
+// parameters and the tuning switches. It touches no device: tests/test_ivf_pq_plan_cpu.py pins it through cuvsAmdIvfPqSearchPlan.
+enum class pq_path : int {
+  lut_one_phase    = 0,  // pq_scan_kernel over all pairs, no head phase
+  lut_two_phase    = 1,  // pq_scan_kernel: the head phase (nearest probes, cold bounds), then the tail (warm bounds)
+  scan2_tail       = 2,  // head phase on pq_scan_kernel, tail on pq_scan2_kernel
+  matrix_core_tail = 3,  // head phase on the LUT scan, tail on the matrix-core filter (pq_filter_kernel or pq_filter4_kernel)
+  wide             = 4,  // bound-only head phase and tail on the wide matrix-core filter (ivf_pq_wide.hip)
+  all_scores       = 5,  // k > 256: every score of the probed lists, then select_k (non-fused path)
+};
+
+struct pq_search_plan {
+  pq_path path      = pq_path::lut_one_phase;
+  uint32_t n_probes = 0;
+  bool lut_fp8 = false, acc_half = false, lut_half = false, bits8 = false;
+  bool glut         = false;  // the LUT does not fit the LDS: it lives in global memory (L2)
+  bool head1        = false;  // LUT-scan work of the head phase and of handed-back queries on single-pair items (pq3_head_scan)
+  bool overlap      = false;  // two-stream schedule
+  bool big_k        = false;  // 64 < k <= 256
+  bool filter4      = false;  // the matrix-core tail runs pq_filter4_kernel (else pq_filter_kernel)
+  bool shard_coarse = false;  // the coarse search is sharded by query over the ranks of a list shard
+  int qpb = 0, k_scan = 0;
+  size_t smem = 0, glut_stride = 0, largest_total = 0;  // largest_total: the rows of the all-scores path's score matrix
+  unsigned grid = 0;                                    // persistent scan kernels: one workgroup per CU
+  uint32_t head = 0, wheads = 0, head_rows = 0, max_list_len = 0, w_ldx = 0, n_ranges = 0, n_labels = 0;
+  int64_t max_batch = 0, bs_alloc = 0, n_pairs_max = 0, max_items = 0;
+  uint32_t surv_cap = 0, overflow_cap = 0, unit_rows = 0;
+  size_t max_units = 0;
+  bool all_scores() const { return path == pq_path::all_scores; }
+  bool mc_tail() const { return path == pq_path::matrix_core_tail || path == pq_path::wide; }  // both matrix-core paths' buffers
+  int lut_mode() const { return lut_fp8 ? 2 : (lut_half ? 1 : 0); }
+};
+
+// The matrix-core tail can serve the shape and the head bound prunes (pq_len other than 2 and PER_CLUSTER codebooks are
+// decoded by pq_filter4_kernel only)
+bool pq_mc_tail_eligible(const ivf_pq_index& idx, int k, const tuning& tune)
+{
+  return pq3_supported(idx, k) && pq3_bound_useful(idx, k) && tune.pq_scan3 != 0 &&
+         ((idx.pq_len == 2 && idx.codebook_kind == 0) || tune.pq_filter4 != 0);
+}
+
+// largest_total: rows of the n_probes largest lists (k > 256 only; reduced over the ranks by the caller). wide_rows_ready is
+// asked only when every other condition of the wide path holds (it may allocate the decoded rows and synchronise).
+pq_search_plan make_pq_search_plan(const ivf_pq_index& idx, const ivf_pq_search_params& p, int k, int64_t n_queries,
+                                          const tuning& tune, int num_cus, size_t ivf_batch_limit, size_t largest_total,
+                                          const std::function<bool()>& wide_rows_ready)
+{
+  pq_search_plan pl;
+  const uint32_t n_probes = pl.n_probes = std::min<uint32_t>(p.n_probes, idx.n_lists);
+  // fp8 LUT (the reference's fp_8bit<5, signed>): entries are rounded through that type and kept in the score type
+  pl.lut_fp8          = p.lut_dtype == 8 || p.lut_dtype == 3;
+  pl.acc_half         = p.lut_dtype != 0 && p.internal_distance_dtype == 2;
+  pl.lut_half         = pl.lut_fp8 ? pl.acc_half : p.lut_dtype != 0;
+  pl.bits8            = idx.pq_bits == 8 && idx.pq_dim == 64;  // FAST4 path: 4 full 16-byte chunks
+  const bool large_k  = k > 256;  // beyond the register top lists: non-fused path (ivf_common.hpp)
+  pl.big_k            = k > 64 && !large_k;
+  pl.k_scan           = large_k ? 1 : k;  // top-list length the scan kernel is launched with
+  pl.grid             = (unsigned)std::max(8, num_cus / 8 * 8);
+  pl.largest_total    = largest_total;
+  const size_t lds_cap = 160 * 1024;
+
+  // choose the widest interleave (queries per work item) whose LUT fits the 160 KiB LDS
+  int qpb = 0;
+  size_t smem = 0;
+  if (!pl.lut_half) {
+    if ((smem = scan_smem_bytes<float, float, 2>(idx, pl.k_scan)) <= lds_cap) qpb = 2;
+    else if ((smem = scan_smem_bytes<float, float, 1>(idx, pl.k_scan)) <= lds_cap) qpb = 1;
+  } else {
+    if ((smem = scan_smem_bytes<__half, float, 4>(idx, pl.k_scan)) <= lds_cap) qpb = 4;
+    else if ((smem = scan_smem_bytes<__half, float, 2>(idx, pl.k_scan)) <= lds_cap) qpb = 2;
+    else if ((smem = scan_smem_bytes<__half, float, 1>(idx, pl.k_scan)) <= lds_cap) qpb = 1;
+  }
+  // no fit: the LUT goes to global memory (L2), as the reference does when its LUT exceeds shared memory
+  pl.glut = qpb == 0;
+  if (pl.glut) {
+    qpb  = pl.lut_half ? 4 : 2;  // 8-byte entries
+    smem = scan_layout(0, qpb, idx.rot_dim, (uint32_t)pl.k_scan).total;
+    CUVS_EXPECTS(smem <= lds_cap, "ivf_pq::search: rot_dim %u / k %d do not fit 160 KiB of LDS", idx.rot_dim, pl.k_scan);
+    pl.glut_stride = ((size_t)idx.pq_dim * idx.pq_book * 8 /* 4 x fp16 or 2 x fp32 */ + 255) & ~size_t(255);
+  }
+  pl.qpb  = qpb;
+  pl.smem = smem;
+
+  // The wide matrix-core path (ivf_pq_wide.hip): shapes pq_filter4_kernel does not decode (rot_dim beyond 256, pq_len not a power
+  // of two) and searches whose k is too large a fraction of ONE list for its bound to prune (pq3_bound_useful) - the bound then
+  // comes from the union of `wheads` head lists. Not on a list shard, batches large enough for a head phase. (A pre-filter is applied
+  // by the emit pass - rejected rows get the value -inf, so the k rows whose exact scores make the bound are admissible ones - and by
+  // the re-score.)
+  const bool mc_ok = pq_mc_tail_eligible(idx, k, tune);
+  if (!large_k && n_probes > 8 && n_queries >= 256 && tune.pq_scan3 != 0 && tune.pq_wide != 0 && tune.pq_head_probes < 0 &&
+      idx.shard_world <= 1 && idx.shard_comm == nullptr && pqw_supported(idx, k) && !mc_ok) {
+    pl.wheads = tune.pq_wide_heads > 0 ? std::min<uint32_t>((uint32_t)tune.pq_wide_heads, n_probes / 2) : pqw_heads(idx, k, n_probes);
+    if (pl.wheads > 0 && !wide_rows_ready()) pl.wheads = 0;  // (no room for the decoded rows)
+  }
+  const bool usew = pl.wheads > 0;
+  for (uint32_t v : idx.h_list_sizes) pl.max_list_len = std::max(pl.max_list_len, v);
+  pl.w_ldx = usew ? (uint32_t)round_up((int64_t)pl.max_list_len + 64, 64) : 0u;
+  // batch of queries per pass (reference: max_internal_batch_size bounds the coarse batch, :814-857)
+  int64_t max_batch = std::max<uint32_t>(1, p.max_internal_batch_size);
+  {
+    // keep the coarse distance matrix and the candidate buffers inside the workspace budget
+    int64_t per_q = (int64_t)idx.n_lists * 4 + (int64_t)n_probes * pl.k_scan * 8 + (int64_t)idx.rot_dim * 4 + idx.dim * 4;
+    if (large_k) per_q += (int64_t)largest_total * 8;
+    // the matrix-core tail phase's buffers, per (query, probe) pair: fp16 B operand, threshold, probe ranks of the pool, >= 16
+    // survivor entries, a fallback work item, two unit descriptors' share, norms and grouping scratch of the two-stream schedule
+    if (!large_k && (pq3_supported(idx, k) || usew) && tune.pq_scan3 != 0)
+      per_q += (int64_t)n_probes * ((int64_t)idx.rot_dim * 2 + (int64_t)k * 4 + 128 + 16 + 4 + 16 + 8);
+    if (usew) per_q += (int64_t)pl.wheads * ((int64_t)pl.w_ldx * 4 + 32) + (int64_t)k * (8 + 32 * 8);  // values of the head lists' rows, the k best
+    int64_t fit   = std::max<int64_t>(1, (int64_t)ivf_batch_limit / per_q);
+    max_batch     = balanced_batch(n_queries, std::min(max_batch, fit));  // (the same on every rank of a list shard: same inputs)
+  }
+  pl.max_batch   = max_batch;
+  pl.bs_alloc    = std::min<int64_t>(max_batch, n_queries);
+  pl.n_pairs_max = pl.bs_alloc * n_probes;
+  // Two-phase schedule: the `head` nearest probes of every query are scanned first (labels 0..n_lists-1), the
+  // rest afterwards (labels n_lists..2 n_lists-1). After the head phase each query's k-th bound (query_kth) is
+  // already close to final, which is what makes the early stop in the scan loop bite. Results do not depend on
+  // the order in which pairs are scanned.
+  // (measured at 100M x 128, n_probes 128: batch 1000 3.2 vs 4.0 ms with the head phase, batch 100 1.7 vs 1.3 ms without:
+  // a second launch and a twice as long label range only pay off once the batch is large)
+  uint32_t head = (n_probes > 8 && n_queries >= 256 && !large_k) ? 1u : 0u;
+  if (tune.pq_head_probes >= 0) head = std::min<uint32_t>((uint32_t)tune.pq_head_probes, n_probes);
+  // signed LUT entries: no early stop in the LUT scan kernels - unless the tail phase runs on the matrix-core filter,
+  // which needs no non-negativity (a full-score bound): then the head phase supplies its bounds as for L2
+  const bool metric_ip = idx.metric == M_InnerProduct || idx.metric == M_CosineExpanded;
+  if (metric_ip && !(mc_ok && tune.pq_head_probes != 0)) head = 0;
+  if (usew) head = pl.wheads;
+  pl.head = head;
+  const bool sharded = idx.shard_world > 1;  // list-sharded index: foreign probes go to a bucket that is never scanned
+  pl.n_ranges        = head > 0 ? 2 * idx.n_lists : idx.n_lists;
+  pl.n_labels        = pl.n_ranges + (sharded ? 1u : 0u);
+  // (with the matrix-core tail phase the head pairs become single-pair items: one item per head pair on top of the
+  // qpb-pair items of the tail labels - the bound used to leave them out and the item array ran over by (queries x head)
+  // items whenever a batch was large against the number of lists: found in round 4 by a 1500-query x 24-list test)
+  pl.max_items = pl.n_pairs_max / qpb + pl.bs_alloc * (int64_t)head + pl.n_labels + 1;
+  // warm-bounds phase on the matrix cores (ivf_pq_scan3.hip): decode + MFMA filter, exact re-score of the survivors.
+  // pq_filter4_kernel serves L2 and cosine; unnormalised inner products (loose margins: ~8x the survivors per pair) keep
+  // pq_filter_kernel, whose per-lane survivor loop is cheaper at that rate (C3 shape: 3.9 vs 6.7 ms)
+  const bool use3 = !usew && head > 0 && mc_ok;
+  pl.filter4      = use3 && tune.pq_filter4 != 0 && (idx.metric != M_InnerProduct || idx.pq_len != 2 || idx.codebook_kind != 0);
+  if (usew || use3) {
+    pl.max_units = pq3_max_units(idx, pl.n_pairs_max, &pl.unit_rows, pl.filter4);
+    pl.surv_cap  = (uint32_t)std::min<int64_t>(std::max<int64_t>(pl.n_pairs_max * 16, 1 << 22), 1 << 28);
+    // (the wide path at large k: a query has at least k survivors by construction and a few times k with the margins of fp16
+    // scores - 1200 per query measured at k = 256 of 1.4 k-row lists - and the head pairs' rows within the bound join them)
+    if (usew) pl.surv_cap = (uint32_t)std::min<int64_t>(std::max<int64_t>((int64_t)pl.surv_cap, pl.bs_alloc * (int64_t)k * 32), 1 << 28);
+    if (tune.pq3_surv_cap > 0) pl.surv_cap = (uint32_t)tune.pq3_surv_cap;
+    pl.overflow_cap = tune.pq3_surv_cap > 0 ? (uint32_t)tune.pq3_surv_cap : (1u << 22);
+  }
+  // two-stream schedule (the bench shape and every other search whose head phase is one single-pair item per query and whose
+  // tail phase runs pq_filter4_kernel): grouping, work units and B operands on the helper stream, next to the head kernel
+  pl.overlap = use3 && pl.filter4 && head == 1 && !pl.glut && tune.pq_overlap != 0;
+  // Partial head (two-stream schedule only: the head items come straight from the probes): the head phase scores the first
+  // head_rows rows of a query's nearest list - its k-th best of those bounds the query's final k-th score like the whole list's
+  // does, a little less tightly - and the list's remaining rows are screened by the filter with all the other probes.
+  // (default rule: 0, see DESIGN 3.1f - set by measurement; a bound needs a few times k rows to mean anything)
+  if (pl.overlap && tune.pq_head_rows >= 0) {
+    pl.head_rows = (uint32_t)tune.pq_head_rows / 64u * 64u;
+    if (pl.head_rows != 0u && pl.head_rows < 4u * (uint32_t)k) pl.head_rows = 0u;
+  }
+  // the tail phase (warm bounds) of the common configuration runs pq_scan2_kernel on items of 2 * qpb pairs
+  // (8 pairs whatever the LUT type: two groups of four with an fp16 LUT, four groups of two with an fp32 LUT)
+  const bool use2 = head > 0 && pl.bits8 && idx.pq_len == 2 && idx.codebook_kind == 0 && k <= 64 &&  // (k <= 64 excludes the non-fused path)
+                    ((pl.lut_half && qpb == 4) || (!pl.lut_half && qpb == 2)) && tune.pq_scan2 != 0 && !(use3 || usew);
+  // with the matrix-core tail phase the LUT scan only sees the head pairs - nearly always one query per list at the
+  // bench shape (10k queries, 16384 lists) - and the pairs of handed-back queries: single-query items and a
+  // single-query LUT (a quarter of the LUT build and of the accumulate work of the 4-query interleave)
+  // (the wide path: pq_head_kernel only serves the pairs of handed-back queries, when its LUT fits next to its score keys)
+  pl.head1 = (use3 && !pl.glut) ||
+             (usew && !pl.glut && idx.rot_dim <= 256 /* its residual buffers */ && (size_t)idx.pq_dim * 256 * (pl.lut_half ? 2 : 4) <= 96 * 1024);
+  // list-sharded index with a communicator: the coarse search is sharded by QUERY - this rank ranks the lists for its
+  // slice of the batch and one all-gather of the probe lists (n_probes x 4 B per query) replaces world - 1 replicas of
+  // the coarse GEMM + select_k (the same deterministic kernels on the same inputs: identical probes)
+  pl.shard_coarse = idx.shard_comm != nullptr && p.coarse_search_dtype == 0 && !tune.shard_coarse_replicated;  // (one rank: the same calls)
+  pl.path = large_k ? pq_path::all_scores
+          : usew    ? pq_path::wide
+          : use3    ? pq_path::matrix_core_tail
+          : head == 0 ? pq_path::lut_one_phase
+          : use2    ? pq_path::scan2_tail
+                    : pq_path::lut_two_phase;
+  return pl;
+}
+
+// per-search scratch, sized from the plan (a buffer the plan's path does not use is empty)
+struct pq_search_scratch {
+  dev_buf<float> qf, rot_q, qc;          // qc: queries in the coarse type
+  dev_buf<uint32_t> probes, sorted_pairs, pair_off, item_off, phase_labels;
+  dev_buf<work_item> items;
+  dev_buf<float> cand_d;                 // per-pair candidate rows (all-scores path: every score of the probed lists)
+  dev_buf<uint32_t> cand_i, pair_seg;
+  dev_buf<float> top_d;
+  dev_buf<uint32_t> top_i, query_kth, tickets;
+  // the matrix-core tail (both paths)
+  dev_buf<uint32_t> cand_r, qstate, unit_off;
+  dev_buf<uint2> surv;
+  dev_buf<uint4> units3, overflow3;      // 32-byte unit descriptors, overflow entries
+  dev_buf<work_item> fb_items;
+  dev_buf<uint4> bq3;                    // fp16 B operands of the tail pairs (the wide path: in blocks of 32 pairs per list, every list's last block padded)
+  dev_buf<float> thr3;
+  // the wide path's bound-only head phase: values of every (head pair, row), the k best of every query, the head pairs' thresholds
+  dev_buf<float> w_x, w_kv, w_thr, w_c;
+  dev_buf<uint32_t> w_ki, w_blk, w_bt;
+  dev_buf<float4> w_nm;
+  // two-stream schedule
+  dev_buf<work_item> hitems;
+  dev_buf<uint32_t> hpairs;              // + the item count
+  dev_buf<float4> pair_norms;
+  dev_buf<uint32_t> group_scratch;       // cursors + second buffer of group_pairs
+  // global-memory LUT, one per workgroup; CUVS_AMD_SCAN_DEBUG bits 128 / 512: per-wave statistics of the scan kernels
+  dev_buf<char> glut_buf;
+  dev_buf<unsigned long long> stats;
+
+  pq_search_scratch(resources& res, const ivf_pq_index& idx, const ivf_pq_search_params& p, const pq_search_plan& pl, int k)
+  {
+    const size_t bs = (size_t)pl.bs_alloc, np = (size_t)pl.n_pairs_max, nl = idx.n_lists;
+    const bool mc = pl.mc_tail(), w = pl.path == pq_path::wide, ov = pl.overlap, f4w = pl.filter4 || w;
+    const size_t wh = w ? bs * pl.wheads : 0, scores = pl.all_scores() ? bs * pl.largest_total : np * k;
+    qf = dev_buf<float>(res, bs * idx.dim); rot_q = dev_buf<float>(res, bs * idx.rot_dim);
+    qc = dev_buf<float>(res, p.coarse_search_dtype != 0 ? bs * idx.dim : 0);
+    probes = dev_buf<uint32_t>(res, np + (size_t)std::max(1, idx.shard_world) * pl.n_probes);  // + slice padding
+    sorted_pairs = dev_buf<uint32_t>(res, np);
+    pair_off = dev_buf<uint32_t>(res, pl.n_labels + 1); item_off = dev_buf<uint32_t>(res, pl.n_labels + 1);
+    phase_labels = dev_buf<uint32_t>(res, (pl.head > 0 || idx.shard_world > 1) ? np : 0);
+    items = dev_buf<work_item>(res, (size_t)pl.max_items);
+    cand_d = dev_buf<float>(res, scores); cand_i = dev_buf<uint32_t>(res, scores);
+    pair_seg = dev_buf<uint32_t>(res, pl.all_scores() ? np : 0);
+    top_d = dev_buf<float>(res, bs * k); top_i = dev_buf<uint32_t>(res, bs * k);
+    query_kth = dev_buf<uint32_t>(res, bs); tickets = dev_buf<uint32_t>(res, 4 * 8 * 32);
+    cand_r = dev_buf<uint32_t>(res, mc ? np * k : 0); qstate = dev_buf<uint32_t>(res, mc ? 4 * bs + 8 + pq3_regions(res) : 0);
+    unit_off = dev_buf<uint32_t>(res, mc ? nl + 1 : 0); surv = dev_buf<uint2>(res, pl.surv_cap);
+    units3 = dev_buf<uint4>(res, 2 * pl.max_units); overflow3 = dev_buf<uint4>(res, (size_t)2 * pl.overflow_cap);
+    fb_items = dev_buf<work_item>(res, mc ? np : 0);
+    bq3 = dev_buf<uint4>(res, f4w ? (np + (w ? (size_t)32 * (nl + 1) : 0)) * (idx.rot_dim / 8) : 0);
+    thr3 = dev_buf<float>(res, f4w ? np : 0);
+    w_x = dev_buf<float>(res, w ? bs * pl.wheads * pl.w_ldx : 0); w_kv = dev_buf<float>(res, w ? bs * k : 0);
+    w_thr = dev_buf<float>(res, wh); w_c = dev_buf<float>(res, wh);
+    w_ki = dev_buf<uint32_t>(res, w ? bs * k : 0); w_blk = dev_buf<uint32_t>(res, w ? nl + 1 : 0);
+    w_bt = dev_buf<uint32_t>(res, w ? 2 * bs : 0); w_nm = dev_buf<float4>(res, wh);
+    hitems = dev_buf<work_item>(res, ov ? bs : 0); hpairs = dev_buf<uint32_t>(res, ov ? bs + 1 : 0);
+    pair_norms = dev_buf<float4>(res, ov ? np : 0); group_scratch = dev_buf<uint32_t>(res, ov ? np + pl.n_labels + 1 : 0);
+    glut_buf = dev_buf<char>(res, pl.glut_stride * pl.grid);
+    stats = dev_buf<unsigned long long>(res, (res.tune.scan_debug & (128 | 512)) ? (size_t)ST_COUNT * pl.grid * kScanWaves : 0);
+  }
+};
+
+// Between fork and join the helper stream's kernels read and write scratch blocks that belong to the handle's stream
+// (sorted_pairs, pair_off, item_off, items, group_scratch, bq3, pair_norms, units3, ...). If anything throws in between
+// (a HIP error, a shard collective's timeout), unwinding would hand those blocks back to the handle's scratch cache while
+// the helper stream may still be using them, and the next call on the handle's stream would re-use them at once. The guard
+// is declared AFTER the pq_search_scratch (destroyed first): while armed, its destructor drains the helper stream.
+struct aux_fork_guard {
+  hipStream_t s = nullptr;
+  bool armed    = false;
+  ~aux_fork_guard() { if (armed && s != nullptr) (void)hipStreamSynchronize(s); }
+};
+
+// what every step of a batch reads
+struct pq_search_ctx {
+  resources& res;   // the handle's stream
+  resources& gres;  // the stream the grouping and the tail phase's preparation are queued on (the helper stream when overlapping)
+  const ivf_pq_search_params& p;
+  const ivf_pq_index& idx;
+  const pq_search_plan& pl;
+  pq_search_scratch& s;
+  aux_fork_guard& fork_guard;
+  int k;
+  const uint32_t* filter_bits;
+};
+
+// ------------------------------------------------------------------ CUVS_AMD_SCAN_DEBUG reporting
+void report_head_stats(resources& res, const unsigned long long* d_stats)  // bit 2048
+{
+  auto hs = to_host(res, d_stats, 8);
+  const double n = (double)std::max<unsigned long long>(1, hs[5]);
+  fprintf(stderr, "[pq_head] items %llu; workgroup cycles per item: header %.0f, LUT %.0f, scores %.0f, select %.0f, output %.0f\n", hs[5],
+          hs[0] / n, hs[1] / n, hs[2] / n, hs[3] / n, hs[4] / n);
+}
+
+void report_filter_stats(resources& res, const unsigned long long* d_stats, const uint32_t* counters)  // bit 1024
+{
+  auto hs = to_host(res, d_stats, 8);
+  g_pq3_last_stats[0] = hs[0]; g_pq3_last_stats[1] = hs[1]; g_pq3_last_stats[2] = hs[2]; g_pq3_last_stats[3] = hs[7];
+  fprintf(stderr, "[pq_scan3] units %llu; wave cycles per unit: prologue %.0f, loop %.0f (slow path %.0f); per subtile %.0f\n", hs[7],
+          (double)hs[4] / std::max<unsigned long long>(1, hs[7]), (double)hs[5] / std::max<unsigned long long>(1, hs[7]),
+          (double)hs[6] / std::max<unsigned long long>(1, hs[7]), (double)hs[5] / std::max<unsigned long long>(1, hs[2]));
+  auto hc = to_host(res, counters, 2);
+  g_pq3_last_stats[4] = hc[0]; g_pq3_last_stats[5] = hc[1];
+  fprintf(stderr, "[pq_scan3] overflow entries %u\n", hc[1]);
+  hc[1] = hc[0];
+  fprintf(stderr, "[pq_scan3] pairs screened %llu, survivors %llu (%.4f%%), subtiles %llu (slow path %llu), fallback pairs %u\n",
+          hs[0], hs[1], 100.0 * hs[1] / (double)std::max<unsigned long long>(1, hs[0]), hs[2], hs[3], hc[1]);
+}
+
+void report_scan_stats(resources& res, const dev_buf<unsigned long long>& stats, unsigned grid, int dbg)  // bits 128 / 512 / 4096
+{
+  std::vector<unsigned long long> hw(stats.n);
+  HIP_TRY(hipMemcpyAsync(hw.data(), stats.data(), stats.bytes(), hipMemcpyDeviceToHost, res.stream));
+  HIP_TRY(hipStreamSynchronize(res.stream));
+  unsigned long long h[ST_COUNT] = {};
+  for (size_t i = 0; i < hw.size(); ++i) h[i % ST_COUNT] += hw[i];
+  const double w = 1.0 / (16.0 * grid);  // wave cycles -> average cycles per wave
+  if (dbg & 4096) {  // per-wave view of the filter pass (which wave of a workgroup runs late?)
+    for (int which : {(int)ST_SCAN, (int)ST_ALIVE2, (int)ST_F_GATHER, (int)ST_F_FLUSH, (int)ST_STAGE2, (int)ST_CAND, (int)ST_S2_CALLS}) {
+      fprintf(stderr, "[pq_scan per-wave stat %d, Mcycles]", which);
+      for (int wv = 0; wv < kScanWaves; ++wv) {
+        unsigned long long t = 0;
+        for (unsigned b = 0; b < grid; ++b) t += hw[((size_t)b * kScanWaves + wv) * ST_COUNT + which];
+        fprintf(stderr, " %.2f", (double)t / grid * 1e-6);
+      }
+      fprintf(stderr, "\n");
+    }
+  }
+  fprintf(stderr,
+          "[pq_scan stats] items %llu rows %llu queued %llu (%.2f%%) stage2 calls %llu alive after chunk1/2/3 %llu/%llu/%llu"
+          " | cycles per wave: header %.3g lut %.3g scan %.3g (stage2 %.3g) merge+sync %.3g\n",
+          h[ST_ITEMS], h[ST_ROWS], h[ST_QUEUED], 100.0 * h[ST_QUEUED] / (double)std::max<unsigned long long>(1, h[ST_ROWS]),
+          h[ST_S2_CALLS], h[ST_ALIVE1], h[ST_ALIVE2], h[ST_ALIVE3], h[ST_HEADER] * w, h[ST_LUT] * w, h[ST_SCAN] * w,
+          h[ST_STAGE2] * w, (double)(h[ST_MERGE] - h[ST_HEADER] - h[ST_LUT] - h[ST_SCAN]) * w);
+  fprintf(stderr, "[pq_scan2 waits, cycles per wave] after filter LUT %.3g, after filter pass %.3g, before LUT B %.3g, after exact LUT "
+          "%.3g, after exact pass %.3g, merge %.3g | filter pass: code-load wait %.3g, gather block %.3g, flush %.3g\n",
+          h[ST_ALIVE1] * w, h[ST_ALIVE2] * w, h[ST_S2_CALLS] * w, h[ST_ALIVE3] * w, h[ST_CAND] * w, h[ST_MERGE] * w,
+          h[ST_F_LOAD] * w, h[ST_F_GATHER] * w, h[ST_F_FLUSH] * w);
+}
+
+// ------------------------------------------------------------------ launches
+// The LUT-scan launch ladder: pq_scan_kernel at the plan's LUT / score types, interleave and LUT placement - or, for the tail
+// phase of the pq_scan2 path, pq_scan2_kernel
+void launch_lut_scan(resources& res, const pq_search_plan& pl, const scan_args& a, bool tail = false)
+{
+  const unsigned grid = pl.grid;
+  if (tail && pl.path == pq_path::scan2_tail) {
+    if (!pl.lut_half)      launch_scan2<float, float, 2, 4>(res, a, grid);
+    else if (!pl.acc_half) launch_scan2<__half, float, 4, 2>(res, a, grid);
+    else                   launch_scan2<__half, __half, 4, 2>(res, a, grid);
+    return;
+  }
+  const size_t smem = pl.smem;
+  const bool bits8 = pl.bits8, big_k = pl.big_k;
+  if (pl.glut) {
+    if (!pl.lut_half)      launch_scan_glut<float, float, 2>(res, a, smem, grid, big_k);
+    else if (!pl.acc_half) launch_scan_glut<__half, float, 4>(res, a, smem, grid, big_k);
+    else                   launch_scan_glut<__half, __half, 4>(res, a, smem, grid, big_k);
+    return;
+  }
+  if (!pl.lut_half) {
+    if (pl.qpb == 2) launch_scan_qpb<float, float, 2>(res, a, smem, grid, bits8, big_k);
+    else             launch_scan_qpb<float, float, 1>(res, a, smem, grid, bits8, big_k);
+  } else if (!pl.acc_half) {
+    if (pl.qpb == 4)      launch_scan_qpb<__half, float, 4>(res, a, smem, grid, bits8, big_k);
+    else if (pl.qpb == 2) launch_scan_qpb<__half, float, 2>(res, a, smem, grid, bits8, big_k);
+    else                  launch_scan_qpb<__half, float, 1>(res, a, smem, grid, bits8, big_k);
+  } else {
+    if (pl.qpb == 4)      launch_scan_qpb<__half, __half, 4>(res, a, smem, grid, bits8, big_k);
+    else if (pl.qpb == 2) launch_scan_qpb<__half, __half, 2>(res, a, smem, grid, bits8, big_k);
+    else                  launch_scan_qpb<__half, __half, 1>(res, a, smem, grid, bits8, big_k);
+  }
+}
+
+// single-pair work items (pq3_head_scan): scores of the whole list in LDS, k smallest selected there
+void launch_head_scan(const pq_search_ctx& c, const scan_args& sa)
+{
+  pq3_head h{};
+  h.items = sa.items; h.item_begin = sa.item_begin; h.item_end = sa.item_end; h.xcd_ticket = sa.xcd_ticket;
+  h.sorted_pairs = sa.sorted_pairs; h.rot_queries = sa.rot_queries; h.cand_d = sa.out_d; h.cand_i = sa.out_i;
+  h.query_kth = sa.query_kth; h.n_probes = c.pl.n_probes; h.k = (uint32_t)c.k; h.max_list_len = c.pl.max_list_len; h.is_ip = sa.is_ip;
+  h.lut_mode = c.pl.lut_mode(); h.acc_half = c.pl.acc_half ? 1 : 0; h.filter_bits = c.filter_bits;
+  h.one_shot = sa.one_shot; h.row_limit = sa.row_limit;
+  dev_buf<unsigned long long> hst(c.res, (sa.dbg & 2048) ? 8 : 0);
+  if (sa.dbg & 2048) HIP_TRY(hipMemsetAsync(hst.data(), 0, hst.bytes(), c.res.stream));
+  h.stats = hst.data();
+  pq3_head_scan(c.res, c.idx, h);
+  if (sa.dbg & 2048) report_head_stats(c.res, hst.data());
+}
+
+// the tail phase on the matrix cores (pq_filter_kernel / pq_filter4_kernel, or the wide filter), the LUT scan of the queries the
+// filter hands back, and the merge of head lists and survivor pool into top_d / top_i
+void run_filter_tail(const pq_search_ctx& c, scan_args a, int64_t nq)
+{
+  resources& res = c.res;
+  const pq_search_plan& pl = c.pl;
+  pq_search_scratch& s = c.s;
+  const int64_t bs = pl.bs_alloc;
+  const bool wide = pl.path == pq_path::wide;
+  HIP_TRY(hipMemsetAsync(s.qstate.data(), 0, s.qstate.bytes(), res.stream));
+  pq3_run r{};
+  r.pair_norms = s.pair_norms.data(); r.head_rows = pl.head_rows;
+  r.nq = nq; r.n_probes = pl.n_probes; r.k = (uint32_t)c.k; r.head = pl.head; r.is_ip = a.is_ip;
+  r.lut_mode = pl.lut_mode(); r.acc_half = pl.acc_half ? 1 : 0;
+  r.sorted_pairs = s.sorted_pairs.data(); r.pair_off = s.pair_off.data(); r.probes = s.probes.data();
+  r.rot_queries = s.rot_q.data(); r.query_kth = s.query_kth.data();
+  r.cand_d = s.cand_d.data(); r.cand_i = s.cand_i.data(); r.cand_r = s.cand_r.data();
+  r.qflag = s.qstate.data(); r.qcnt = s.qstate.data() + bs; r.counters = s.qstate.data() + 2 * bs;
+  r.surv_cnt = s.qstate.data() + 2 * bs + 2;
+  r.ov_cnt = s.qstate.data() + 2 * bs + 4 + pq3_regions(res); r.ov_off = r.ov_cnt + bs;
+  r.surv = s.surv.data(); r.surv_cap = pl.surv_cap; r.units = s.units3.data(); r.unit_off = s.unit_off.data();
+  r.unit_rows = pl.unit_rows; r.xcd_ticket = s.tickets.data() + 2 * 8 * 32; r.fb_items = s.fb_items.data();
+  r.filter_bits = c.filter_bits; r.overflow = s.overflow3.data(); r.overflow_cap = pl.overflow_cap;
+  r.bq = (pl.filter4 || wide) ? s.bq3.data() : nullptr; r.thr = s.thr3.data();
+  dev_buf<unsigned long long> st3(res, (a.dbg & 1024) ? 8 : 0);
+  if (a.dbg & 1024) HIP_TRY(hipMemsetAsync(st3.data(), 0, st3.bytes(), res.stream));
+  r.stats = st3.data(); r.filter_dbg = (a.dbg >> 16) & 255;  // CUVS_AMD_SCAN_DEBUG bits 16..23
+  if (pl.overlap) {
+    // the helper stream: work units, B operands and norms of the tail pairs (nothing here reads the head phase's bounds);
+    // join; then thresholds, filter and re-score behind the head kernel (and the bound all-reduce) on the handle's stream
+    r.stage = 1;
+    pq3_tail(c.gres, c.idx, r);
+    HIP_TRY(hipEventRecord(res.aux_events[1], c.gres.stream));
+    HIP_TRY(hipStreamWaitEvent(res.stream, res.aux_events[1], 0));
+    c.fork_guard.armed = false;  // joined: everything the helper stream was given is ordered before the handle's stream again
+    r.stage = 2;
+  }
+  if (wide) {
+    const pqw_bufs hb{s.w_x.data(), pl.w_ldx, s.w_kv.data(), s.w_ki.data(), s.w_thr.data(), s.w_c.data(), s.w_nm.data(),
+                      s.tickets.data(), s.w_blk.data(), s.w_bt.data()};
+    const bool ok = pqw_head_bounds(res, c.idx, r, hb);
+    CUVS_EXPECTS(ok, "ivf_pq: the wide path's decoded rows are gone");
+    pqw_tail(res, c.idx, r, hb);
+  } else {
+    pq3_tail(res, c.idx, r);
+  }
+  // queries the filter could not serve (no finite bound, operands beyond fp16, full pool): LUT scan of their pairs
+  a.items = s.fb_items.data(); a.item_begin = nullptr; a.item_end = r.counters;
+  a.xcd_ticket = s.tickets.data() + 3 * 8 * 32;
+  if (pl.head1) launch_head_scan(c, a); else launch_lut_scan(res, pl, a);
+  pq3_merge(res, r, s.top_d.data(), s.top_i.data());
+  if (a.dbg & 1024) report_filter_stats(res, st3.data(), r.counters);
+}
+
+// ------------------------------------------------------------------ one batch of queries
+// coarse search -> labels -> work items -> head phase -> tail -> merge -> postprocess
+void pq_search_batch(const pq_search_ctx& c, const void* queries, elem_t et, int64_t q0, int64_t nq, int64_t* neighbors,
+                            float* distances)
+{
+  resources& res = c.res;
+  const ivf_pq_index& idx = c.idx;
+  const pq_search_plan& pl = c.pl;
+  pq_search_scratch& s = c.s;
+  const int k = c.k;
+  const uint32_t n_probes = pl.n_probes;
+  const int64_t n_pairs = nq * n_probes;
+  load_range_as_float(res, queries, et, false /* the C layer guarantees device-accessible queries */, idx.dim, q0, nq, s.qf.data());
+  if (idx.metric == M_CosineExpanded) normalize_rows(res, s.qf.data(), nq, idx.dim);
+  if (pl.shard_coarse) {  // this rank's slice of the batch, then one all-gather of the probe lists
+    const int64_t slice = (nq + idx.shard_world - 1) / idx.shard_world;
+    const int64_t s0    = std::min<int64_t>(nq, (int64_t)idx.shard_rank * slice);
+    const int64_t s1    = std::min<int64_t>(nq, s0 + slice);
+    if (s1 > s0)
+      select_clusters(res, idx, s.qf.data() + s0 * idx.dim, s1 - s0, n_probes,
+                      s.probes.data() + (size_t)idx.shard_rank * slice * n_probes, 0, s.qc.data());
+    shard_allgather_inplace_u32(res, idx.shard_comm, s.probes.data(), (size_t)slice * n_probes);
+  } else {
+    select_clusters(res, idx, s.qf.data(), nq, n_probes, s.probes.data(), c.p.coarse_search_dtype, s.qc.data());
+  }
+  rotate_queries(res, idx, s.qf.data(), s.qc.data(), nq, c.p.coarse_search_dtype, s.rot_q.data());  // ivf_pq_search.cuh:995-1017
+  if (c.p.coarse_search_dtype != 0 && idx.metric == M_CosineExpanded) normalize_rows(res, s.rot_q.data(), nq, idx.rot_dim);
+  // list-major grouping of the (query, probe) pairs
+  const uint32_t* labels = s.probes.data();
+  if (pl.overlap) {  // fork: the helper stream starts behind the probes and the rotated queries
+    pq3_warm(res, idx, true);  // (derived tables of the index: built here, on the handle's stream, if they are not there yet)
+    HIP_TRY(hipEventRecord(res.aux_events[0], res.stream));
+    HIP_TRY(hipStreamWaitEvent(c.gres.stream, res.aux_events[0], 0));
+    c.fork_guard.armed = true;
+  }
+  if (pl.head > 0 || idx.shard_world > 1) {
+    hipLaunchKernelGGL(phase_labels_kernel, dim3(nblk(n_pairs, 256)), dim3(256), 0, c.gres.stream, s.probes.data(),
+                       n_pairs, n_probes, pl.head, idx.n_lists, s.phase_labels.data(), (uint32_t)idx.shard_world,
+                       (uint32_t)idx.shard_rank, pl.n_ranges, idx.list_owner.data(), pl.head_rows != 0u);
+    labels = s.phase_labels.data();
+  }
+  build_work_items(c.gres, labels, n_pairs, pl.n_labels, pl.head1 ? 1 : pl.qpb, s.sorted_pairs.data(), s.pair_off.data(),
+                   s.item_off.data(), s.items.data(), (int)idx.n_lists, pl.path == pq_path::scan2_tail ? 8 : pl.qpb,
+                   pl.overlap ? s.group_scratch.data() : nullptr,
+                   pl.n_ranges /* the shard's bucket of foreign pairs stays as the scatter left it */, n_probes, nq);
+  if (pl.overlap)
+    hipLaunchKernelGGL(head_items_kernel, dim3(nblk(nq, 256)), dim3(256), 0, res.stream, s.probes.data(), nq, n_probes,
+                       (uint32_t)idx.shard_world, (uint32_t)idx.shard_rank, idx.list_owner.data(), s.hitems.data(), s.hpairs.data(),
+                       s.hpairs.data() + pl.bs_alloc);
+  HIP_TRY(hipMemsetAsync(s.query_kth.data(), 0xff, (size_t)nq * sizeof(uint32_t), res.stream));
+  HIP_TRY(hipMemsetAsync(s.tickets.data(), 0, s.tickets.bytes(), res.stream));
+  // per-pair candidate rows start out invalid: the scan only writes the rows of pairs that found something
+  const size_t scores_ld = pl.largest_total;
+  if (pl.mc_tail()) {
+    // matrix-core tail phase: only the head segments of a query's row are read before they are written (the pool behind
+    // them is filled by count, the rows of handed-back queries are reset by reset_flagged_kernel) - no fill of all
+    // n_pairs x k slots (205 MB per batch at the bench shape; on a list shard most of them belong to foreign pairs)
+    hipLaunchKernelGGL(init_head_rows_kernel, dim3(nblk(nq * (int64_t)pl.head * k, 256)), dim3(256), 0, res.stream, s.cand_d.data(),
+                       s.cand_i.data(), nq, (int64_t)n_probes * k, (uint32_t)(pl.head * k));
+  } else if (!pl.all_scores()) {
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s.cand_d.data()), 0x7f7fffff, (size_t)n_pairs * k, res.stream));
+    HIP_TRY(hipMemsetAsync(s.cand_i.data(), 0xff, (size_t)n_pairs * k * sizeof(uint32_t), res.stream));
+  } else {
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s.cand_d.data()), 0x7f7fffff, (size_t)nq * scores_ld, res.stream));
+    HIP_TRY(hipMemsetAsync(s.cand_i.data(), 0xff, (size_t)nq * scores_ld * sizeof(uint32_t), res.stream));
+    hipLaunchKernelGGL(pair_segments_kernel, dim3(nblk(nq, 256)), dim3(256), 0, res.stream, s.probes.data(),
+                       idx.list_sizes.data(), nq, n_probes, s.pair_seg.data());
+  }
+  scan_args a;
+  a.query_kth = s.query_kth.data();
+  a.items = s.items.data(); a.sorted_pairs = s.sorted_pairs.data(); a.n_lists = idx.n_lists;
+  a.rot_queries = s.rot_q.data(); a.centers_rot = idx.centers_rot.data(); a.pq_centers = idx.pq_centers.data();
+  a.per_cluster = idx.codebook_kind == 1;
+  a.codes = idx.codes.data(); a.list_offsets = idx.list_offsets.data(); a.list_sizes = idx.list_sizes.data();
+  a.out_d = s.cand_d.data(); a.out_i = s.cand_i.data();
+  a.all_scores = pl.all_scores() ? s.cand_d.data() : nullptr; a.all_rows = s.cand_i.data(); a.pair_seg = s.pair_seg.data();
+  a.scores_ld = scores_ld;
+  a.n_probes = n_probes; a.rot_dim = idx.rot_dim; a.pq_dim = idx.pq_dim; a.pq_len = idx.pq_len;
+  a.pq_bits = idx.pq_bits; a.n_chunks = idx.n_chunks; a.cpc = idx.codes_per_chunk; a.k = (uint32_t)pl.k_scan;
+  a.is_ip = idx.metric == M_InnerProduct || idx.metric == M_CosineExpanded;
+  a.lut_fp8 = pl.lut_fp8 ? 1 : 0;
+  a.dbg   = res.tune.scan_debug;
+  a.qcap  = (uint32_t)std::max(0, res.tune.pq_qcap);
+  a.filter_bits = c.filter_bits; a.indices = idx.indices.data();
+  a.stats = s.stats.data();
+  if (a.dbg & (128 | 512)) HIP_TRY(hipMemsetAsync(s.stats.data(), 0, s.stats.bytes(), res.stream));
+  a.global_lut_stride = pl.glut_stride;
+  a.global_lut = pl.glut ? s.glut_buf.data() : nullptr;
+  a.xcd_ticket = s.tickets.data();
+  a.item_begin = nullptr; a.item_end = s.item_off.data() + idx.n_lists;
+  if (pl.head > 0) {
+    if (pl.path == pq_path::wide) {
+      // the wide path's head phase is a bound-only pass through the filter: in run_filter_tail, with the tail phase's run description
+    } else if (pl.overlap) {  // head phase straight from the probes (one single-pair item per query), no grouping in its way
+      scan_args ah = a;
+      ah.items = s.hitems.data(); ah.sorted_pairs = s.hpairs.data(); ah.item_end = s.hpairs.data() + pl.bs_alloc;
+      ah.one_shot = (uint32_t)nq;  // one workgroup per item: slots free up item by item, the helper stream's kernels fit in between
+      ah.row_limit = pl.head_rows;
+      launch_head_scan(c, ah);
+    } else if (pl.head1) launch_head_scan(c, a); else launch_lut_scan(res, pl, a);  // head phase: the nearest probes, cold bounds
+    // list-sharded index with a communicator: every rank continues with the bound of the query's globally nearest
+    // probe (one all-reduce of nq keys), not only the rank that owns that probe
+    if (idx.shard_comm != nullptr) shard_allreduce_min_u32(res, idx.shard_comm, s.query_kth.data(), (size_t)nq);
+    a.xcd_ticket = s.tickets.data() + 8 * 32;
+    a.item_begin = s.item_off.data() + idx.n_lists;  a.item_end = s.item_off.data() + 2 * idx.n_lists;
+    if (pl.mc_tail()) run_filter_tail(c, a, nq);
+    else              launch_lut_scan(res, pl, a, /*tail=*/true);  // tail phase: warm bounds
+  } else {
+    launch_lut_scan(res, pl, a);
+  }
+  if (a.dbg & (128 | 512)) report_scan_stats(res, s.stats, pl.grid, a.dbg);
+  // per-query merge of n_probes * k candidates (ivf_pq_search.cuh:646-655); the matrix-core tails merged already (pq3_merge)
+  if (!pl.mc_tail()) {
+    const int64_t row = pl.all_scores() ? (int64_t)scores_ld : (int64_t)n_probes * k;
+    select_k<uint32_t, uint32_t>(res, s.cand_d.data(), s.cand_i.data(), nq, row, row, k, s.top_d.data(), s.top_i.data(), true);
+  }
+  const float sc = ivf_pq_index::scale(et);
+  hipLaunchKernelGGL(postprocess_kernel, dim3(nblk(nq * k, 256)), dim3(256), 0, res.stream, s.top_i.data(),
+                     s.top_d.data(), nq * k, idx.indices.data(), idx.metric, sc * sc, neighbors + q0 * k,
+                     distances + q0 * k);
+}
+
+}  // namespace
+
 void ivf_pq_search(resources& res, const ivf_pq_search_params& p, const ivf_pq_index& idx, const void* queries,
                    elem_t et, int64_t n_queries, int k, int64_t* neighbors, float* distances, const uint32_t* filter_bits)
 {
@@ -2072,41 +2630,12 @@ void ivf_pq_search(resources& res, const ivf_pq_search_params& p, const ivf_pq_i
   CUVS_EXPECTS(!idx.dtype_known || et == idx.dtype, "queries dtype differs from the index dtype");
   if (n_queries == 0) return;
   if (idx.shard_comm != nullptr && !idx.shard_stats_valid) shard_exchange_stats(res, idx);
-  const uint32_t n_probes = std::min<uint32_t>(p.n_probes, idx.n_lists);
-  // fp8 LUT (the reference's fp_8bit<5, signed>): entries are rounded through that type and kept in the score type
-  const bool lut_fp8      = p.lut_dtype == 8 || p.lut_dtype == 3;
-  const bool acc_half     = p.lut_dtype != 0 && p.internal_distance_dtype == 2;
-  const bool lut_half     = lut_fp8 ? acc_half : p.lut_dtype != 0;
-  const bool bits8        = idx.pq_bits == 8 && idx.pq_dim == 64;  // FAST4 path: 4 full 16-byte chunks
-  const bool large_k      = k > 256;  // beyond the register top lists: non-fused path (ivf_common.hpp)
-  const bool big_k        = k > 64 && !large_k;
-  const int k_scan        = large_k ? 1 : k;  // top-list length the scan kernel is launched with
-  const size_t lds_cap    = 160 * 1024;
-
-  // choose the widest interleave (queries per work item) whose LUT fits the 160 KiB LDS
-  int qpb = 0;
-  size_t smem = 0;
-  if (!lut_half) {
-    if ((smem = scan_smem_bytes<float, float, 2>(idx, k_scan)) <= lds_cap) qpb = 2;
-    else if ((smem = scan_smem_bytes<float, float, 1>(idx, k_scan)) <= lds_cap) qpb = 1;
-  } else {
-    if ((smem = scan_smem_bytes<__half, float, 4>(idx, k_scan)) <= lds_cap) qpb = 4;
-    else if ((smem = scan_smem_bytes<__half, float, 2>(idx, k_scan)) <= lds_cap) qpb = 2;
-    else if ((smem = scan_smem_bytes<__half, float, 1>(idx, k_scan)) <= lds_cap) qpb = 1;
-  }
-  // no fit: the LUT goes to global memory (L2), as the reference does when its LUT exceeds shared memory
-  const bool glut = qpb == 0;
-  if (glut) {
-    qpb  = lut_half ? 4 : 2;  // 8-byte entries
-    smem = scan_layout(0, qpb, idx.rot_dim, (uint32_t)k_scan).total;
-    CUVS_EXPECTS(smem <= lds_cap, "ivf_pq::search: rot_dim %u / k %d do not fit 160 KiB of LDS", idx.rot_dim, k_scan);
-  }
-
   // rows of the n_probes largest lists: the width of the score matrix of the non-fused path. With a shard communicator
   // attached the batch size derived from it must be the same on every rank (the ranks issue one probe all-gather and
   // one bound all-reduce per batch: different batch counts would hang the collectives), so the maximum over the
   // ranks is used (one 4-byte all-reduce, only on this rarely taken path).
-  size_t largest_total = large_k ? largest_lists_total(idx.h_list_sizes, n_probes) : 0;
+  const bool large_k   = k > 256;
+  size_t largest_total = large_k ? largest_lists_total(idx.h_list_sizes, std::min<uint32_t>(p.n_probes, idx.n_lists)) : 0;
   if (large_k && idx.shard_comm != nullptr) {
     dev_buf<uint32_t> key(res, 1);
     const uint32_t mine = ~(uint32_t)std::min<size_t>(largest_total, 0xfffffffeu);  // min over ~x = max over x
@@ -2114,407 +2643,59 @@ void ivf_pq_search(resources& res, const ivf_pq_search_params& p, const ivf_pq_i
     shard_allreduce_min_u32(res, idx.shard_comm, key.data(), 1);
     largest_total = (size_t)~to_host(res, key.data(), 1)[0];
   }
-  // The wide matrix-core path (ivf_pq_wide.hip): shapes pq_filter4_kernel does not decode (rot_dim beyond 256, pq_len not a power
-  // of two) and searches whose k is too large a fraction of ONE list for its bound to prune (pq3_bound_useful) - the bound then
-  // comes from the union of `wheads` head lists. Not on a list shard, batches large enough for a head phase. (A pre-filter is applied
-  // by the emit pass - rejected rows get the value -inf, so the k rows whose exact scores make the bound are admissible ones - and by
-  // the re-score.)
-  uint32_t wheads = 0;
-  if (!large_k && n_probes > 8 && n_queries >= 256 && res.tune.pq_scan3 != 0 && res.tune.pq_wide != 0 && res.tune.pq_head_probes < 0 &&
-      idx.shard_world <= 1 && idx.shard_comm == nullptr && pqw_supported(idx, k) &&
-      !(pq3_supported(idx, k) && pq3_bound_useful(idx, k) && ((idx.pq_len == 2 && idx.codebook_kind == 0) || res.tune.pq_filter4 != 0))) {
-    wheads = res.tune.pq_wide_heads > 0 ? std::min<uint32_t>((uint32_t)res.tune.pq_wide_heads, n_probes / 2) : pqw_heads(idx, k, n_probes);
-    if (wheads > 0 && !pqw_ready(res, idx)) wheads = 0;  // (no room for the decoded rows)
-  }
-  const bool usew = wheads > 0;
+  const pq_search_plan pl = make_pq_search_plan(idx, p, k, n_queries, res.tune, res.num_cus, res.ivf_batch_limit, largest_total,
+                                                [&] { return pqw_ready(res, idx); });
   if (res.tune.scan_debug & 1024)
-    fprintf(stderr, "[pq_wide] heads %u (supported %d, matrix-core tail of the narrow shapes %d, probes %u, queries %ld, k %d)\n", wheads,
-            (int)pqw_supported(idx, k), (int)(pq3_supported(idx, k) && pq3_bound_useful(idx, k)), n_probes, (long)n_queries, k);
-  uint32_t max_list_len = 0;
-  for (uint32_t v : idx.h_list_sizes) max_list_len = std::max(max_list_len, v);
-  const uint32_t w_ldx = usew ? (uint32_t)round_up((int64_t)max_list_len + 64, 64) : 0u;
-  // batch of queries per pass (reference: max_internal_batch_size bounds the coarse batch, :814-857)
-  int64_t max_batch = std::max<uint32_t>(1, p.max_internal_batch_size);
-  {
-    // keep the coarse distance matrix and the candidate buffers inside the workspace budget
-    int64_t per_q = (int64_t)idx.n_lists * 4 + (int64_t)n_probes * k_scan * 8 + (int64_t)idx.rot_dim * 4 + idx.dim * 4;
-    if (large_k) per_q += (int64_t)largest_total * 8;
-    // the matrix-core tail phase's buffers, per (query, probe) pair: fp16 B operand, threshold, probe ranks of the pool, >= 16
-    // survivor entries, a fallback work item, two unit descriptors' share, norms and grouping scratch of the two-stream schedule
-    if (!large_k && (pq3_supported(idx, k) || usew) && res.tune.pq_scan3 != 0)
-      per_q += (int64_t)n_probes * ((int64_t)idx.rot_dim * 2 + (int64_t)k * 4 + 128 + 16 + 4 + 16 + 8);
-    if (usew) per_q += (int64_t)wheads * ((int64_t)w_ldx * 4 + 32) + (int64_t)k * (8 + 32 * 8);  // values of the head lists' rows, the k best
-    int64_t fit   = std::max<int64_t>(1, (int64_t)res.ivf_batch_limit / per_q);
-    max_batch     = balanced_batch(n_queries, std::min(max_batch, fit));  // (the same on every rank of a list shard: same inputs)
-  }
-  const int64_t bs_alloc = std::min<int64_t>(max_batch, n_queries);
-  const int64_t n_pairs_max = bs_alloc * n_probes;
-  dev_buf<float> qf(res, (size_t)bs_alloc * idx.dim);
-  dev_buf<float> rot_q(res, (size_t)bs_alloc * idx.rot_dim);
-  dev_buf<float> qc(res, p.coarse_search_dtype != 0 ? (size_t)bs_alloc * idx.dim : 0);  // queries in the coarse type
-  dev_buf<uint32_t> probes(res, (size_t)n_pairs_max + (size_t)std::max(1, idx.shard_world) * n_probes);  // + slice padding
-  // Two-phase schedule: the `head` nearest probes of every query are scanned first (labels 0..n_lists-1), the
-  // rest afterwards (labels n_lists..2 n_lists-1). After the head phase each query's k-th bound (query_kth) is
-  // already close to final, which is what makes the early stop in the scan loop bite. Results do not depend on
-  // the order in which pairs are scanned.
-  // (measured at 100M x 128, n_probes 128: batch 1000 3.2 vs 4.0 ms with the head phase, batch 100 1.7 vs 1.3 ms without:
-  // a second launch and a twice as long label range only pay off once the batch is large)
-  uint32_t head = (n_probes > 8 && n_queries >= 256 && !large_k) ? 1u : 0u;
-  if (res.tune.pq_head_probes >= 0) head = std::min<uint32_t>((uint32_t)res.tune.pq_head_probes, n_probes);
-  // signed LUT entries: no early stop in the LUT scan kernels - unless the tail phase runs on the matrix-core filter,
-  // which needs no non-negativity (a full-score bound): then the head phase supplies its bounds as for L2
-  const bool pq3_ok = !large_k && pq3_supported(idx, k) && pq3_bound_useful(idx, k) && res.tune.pq_scan3 != 0 && res.tune.pq_head_probes != 0 &&
-                      ((idx.pq_len == 2 && idx.codebook_kind == 0) || res.tune.pq_filter4 != 0);
-  if ((idx.metric == M_InnerProduct || idx.metric == M_CosineExpanded) && !pq3_ok) head = 0;
-  if (usew) head = wheads;
-  const bool sharded      = idx.shard_world > 1;  // list-sharded index: foreign probes go to a bucket that is never scanned
-  const uint32_t n_ranges = head > 0 ? 2 * idx.n_lists : idx.n_lists;
-  const uint32_t n_labels = n_ranges + (sharded ? 1u : 0u);
-  dev_buf<uint32_t> sorted_pairs(res, (size_t)n_pairs_max), pair_off(res, n_labels + 1), item_off(res, n_labels + 1);
-  dev_buf<uint32_t> phase_labels(res, (head > 0 || sharded) ? (size_t)n_pairs_max : 0);
-  // (with the matrix-core tail phase the head pairs become single-pair items: one item per head pair on top of the
-  // qpb-pair items of the tail labels - the bound used to leave them out and the item array ran over by (queries x head)
-  // items whenever a batch was large against the number of lists: found in round 4 by a 1500-query x 24-list test)
-  const int64_t max_items = n_pairs_max / qpb + bs_alloc * (int64_t)head + n_labels + 1;
-  dev_buf<work_item> items(res, (size_t)max_items);
-  const size_t scores_ld = largest_total;
-  dev_buf<float> cand_d(res, large_k ? (size_t)bs_alloc * scores_ld : (size_t)n_pairs_max * k);
-  dev_buf<uint32_t> cand_i(res, large_k ? (size_t)bs_alloc * scores_ld : (size_t)n_pairs_max * k);
-  dev_buf<uint32_t> pair_seg(res, large_k ? (size_t)n_pairs_max : 0);
-  dev_buf<float> top_d(res, (size_t)bs_alloc * k);
-  dev_buf<uint32_t> top_i(res, (size_t)bs_alloc * k);
-  dev_buf<uint32_t> query_kth(res, (size_t)bs_alloc);
-  dev_buf<uint32_t> tickets(res, 4 * 8 * 32);
-  // warm-bounds phase on the matrix cores (ivf_pq_scan3.hip): decode + MFMA filter, exact re-score of the survivors
-  const bool metric_ip = idx.metric == M_InnerProduct || idx.metric == M_CosineExpanded;
-  // (pq_len other than 2 is decoded by pq_filter4_kernel only)
-  const bool use3 = !usew && head > 0 && !large_k && pq3_supported(idx, k) && pq3_bound_useful(idx, k) && res.tune.pq_scan3 != 0 && ((idx.pq_len == 2 && idx.codebook_kind == 0) || res.tune.pq_filter4 != 0);
-  const bool use3x = use3 || usew;  // the buffers both matrix-core paths need
-  uint32_t unit_rows = 0;
-  const size_t max_units = usew ? pq3_max_units(idx, n_pairs_max, &unit_rows, false) : use3 ? pq3_max_units(idx, n_pairs_max, &unit_rows, res.tune.pq_filter4 != 0 && (idx.metric != M_InnerProduct || idx.pq_len != 2 || idx.codebook_kind != 0)) : 0;
-  uint32_t surv_cap = use3x ? (uint32_t)std::min<int64_t>(std::max<int64_t>(n_pairs_max * 16, 1 << 22), 1 << 28) : 0u;
-  // (the wide path at large k: a query has at least k survivors by construction and a few times k with the margins of fp16 scores -
-  // 1200 per query measured at k = 256 of 1.4 k-row lists - and the head pairs' rows within the bound join them)
-  if (usew) surv_cap = (uint32_t)std::min<int64_t>(std::max<int64_t>((int64_t)surv_cap, bs_alloc * (int64_t)k * 32), 1 << 28);
-  if (use3x && res.tune.pq3_surv_cap > 0) surv_cap = (uint32_t)res.tune.pq3_surv_cap;
-  dev_buf<uint32_t> cand_r(res, use3x ? (size_t)n_pairs_max * k : 0), qstate(res, use3x ? (size_t)4 * bs_alloc + 8 + pq3_regions(res) : 0);
-  dev_buf<uint32_t> unit_off(res, use3x ? (size_t)idx.n_lists + 1 : 0);
-  dev_buf<uint2> surv(res, surv_cap);
-  dev_buf<uint4> units3(res, 2 * max_units);  // 32-byte unit descriptors
-  const uint32_t overflow_cap = use3x ? (res.tune.pq3_surv_cap > 0 ? (uint32_t)res.tune.pq3_surv_cap : (1u << 22)) : 0u;
-  dev_buf<uint4> overflow3(res, (size_t)2 * overflow_cap);
-  dev_buf<work_item> fb_items(res, use3x ? (size_t)n_pairs_max : 0);
-  // pq_filter4_kernel serves L2 and cosine; unnormalised inner products (loose margins: ~8x the survivors per pair) keep
-  // pq_filter_kernel, whose per-lane survivor loop is cheaper at that rate (C3 shape: 3.9 vs 6.7 ms)
-  const bool use_f4 = use3 && res.tune.pq_filter4 != 0 && (idx.metric != M_InnerProduct || idx.pq_len != 2 || idx.codebook_kind != 0);
-  // fp16 B operands of the tail pairs (the wide path: in blocks of 32 pairs per list, every list's last block padded)
-  dev_buf<uint4> bq3(res, (use_f4 || usew) ? ((size_t)n_pairs_max + (usew ? (size_t)32 * (idx.n_lists + 1) : 0)) * (idx.rot_dim / 8) : 0);
-  dev_buf<float> thr3(res, (use_f4 || usew) ? (size_t)n_pairs_max : 0);
-  // the wide path's bound-only head phase: values of every (head pair, row), the k best of every query, the head pairs' thresholds
-  dev_buf<float> w_x(res, usew ? (size_t)bs_alloc * wheads * w_ldx : 0), w_kv(res, usew ? (size_t)bs_alloc * k : 0);
-  dev_buf<float> w_thr(res, usew ? (size_t)bs_alloc * wheads : 0), w_c(res, usew ? (size_t)bs_alloc * wheads : 0);
-  dev_buf<uint32_t> w_ki(res, usew ? (size_t)bs_alloc * k : 0), w_blk(res, usew ? (size_t)idx.n_lists + 1 : 0), w_bt(res, usew ? (size_t)2 * bs_alloc : 0);
-  dev_buf<float4> w_nm(res, usew ? (size_t)bs_alloc * wheads : 0);
-  // two-stream schedule (the bench shape and every other search whose head phase is one single-pair item per query and whose
-  // tail phase runs pq_filter4_kernel): grouping, work units and B operands on the helper stream, next to the head kernel
-  const bool overlap = use3 && use_f4 && head == 1 && !glut && res.tune.pq_overlap != 0;
-  dev_buf<work_item> hitems(res, overlap ? (size_t)bs_alloc : 0);
-  dev_buf<uint32_t> hpairs(res, overlap ? (size_t)bs_alloc + 1 : 0);  // + the item count
-  dev_buf<float4> pair_norms(res, overlap ? (size_t)n_pairs_max : 0);
-  dev_buf<uint32_t> group_scratch(res, overlap ? (size_t)n_pairs_max + n_labels + 1 : 0);  // cursors + second buffer of group_pairs
+    fprintf(stderr, "[pq_wide] heads %u (supported %d, matrix-core tail of the narrow shapes %d, probes %u, queries %ld, k %d)\n", pl.wheads,
+            (int)pqw_supported(idx, k), (int)(pq3_supported(idx, k) && pq3_bound_useful(idx, k)), pl.n_probes, (long)n_queries, k);
+  pq_search_scratch scratch(res, idx, p, pl, k);
   resources aux = res;
-  if (overlap) {
+  if (pl.overlap) {
     ensure_aux_stream(res);
     aux.aux_stream = res.aux_stream;
     aux.stream     = res.aux_stream;
   }
-  resources& gres = overlap ? aux : res;  // the stream the grouping and the tail phase's preparation are queued on
-  // Between fork and join the helper stream's kernels read and write scratch blocks that belong to the handle's stream
-  // (sorted_pairs, pair_off, item_off, items, group_scratch, bq3, pair_norms, units3, ...). If anything throws in between
-  // (a HIP error, a shard collective's timeout), unwinding would hand those blocks back to the handle's scratch cache while
-  // the helper stream may still be using them, and the next call on the handle's stream would re-use them at once. The guard
-  // is declared AFTER every such buffer (destroyed first): while armed, its destructor drains the helper stream.
-  struct aux_fork_guard {
-    hipStream_t s = nullptr;
-    bool armed    = false;
-    ~aux_fork_guard() { if (armed && s != nullptr) (void)hipStreamSynchronize(s); }
-  } fork_guard;
-  fork_guard.s = overlap ? aux.stream : nullptr;
-  // Partial head (two-stream schedule only: the head items come straight from the probes): the head phase scores the first
-  // head_rows rows of a query's nearest list - its k-th best of those bounds the query's final k-th score like the whole list's
-  // does, a little less tightly - and the list's remaining rows are screened by the filter with all the other probes.
-  uint32_t head_rows = 0u;
-  if (overlap) {
-    if (res.tune.pq_head_rows >= 0) head_rows = (uint32_t)res.tune.pq_head_rows / 64u * 64u;
-    else                            head_rows = 0u;  // (default rule: see DESIGN 3.1f - set by measurement)
-    if (head_rows != 0u && head_rows < 4u * (uint32_t)k) head_rows = 0u;  // (a bound needs a few times k rows to mean anything)
-  }
-  const bool q_is_host = false;  // the C layer guarantees device-accessible queries
-
-  for (int64_t q0 = 0; q0 < n_queries; q0 += max_batch) {
-    const int64_t nq      = std::min(max_batch, n_queries - q0);
-    const int64_t n_pairs = nq * n_probes;
-    load_range_as_float(res, queries, et, q_is_host, idx.dim, q0, nq, qf.data());
-    if (idx.metric == M_CosineExpanded) normalize_rows(res, qf.data(), nq, idx.dim);
-    // list-sharded index with a communicator: the coarse search is sharded by QUERY - this rank ranks the lists for its
-    // slice of the batch and one all-gather of the probe lists (n_probes x 4 B per query) replaces world - 1 replicas of
-    // the coarse GEMM + select_k (the same deterministic kernels on the same inputs: identical probes)
-    const bool shard_coarse = idx.shard_comm != nullptr && p.coarse_search_dtype == 0 &&  // (one rank: the same calls)
-                              !res.tune.shard_coarse_replicated;
-    if (shard_coarse) {
-      const int64_t slice = (nq + idx.shard_world - 1) / idx.shard_world;
-      const int64_t s0    = std::min<int64_t>(nq, (int64_t)idx.shard_rank * slice);
-      const int64_t s1    = std::min<int64_t>(nq, s0 + slice);
-      if (s1 > s0)
-        select_clusters(res, idx, qf.data() + s0 * idx.dim, s1 - s0, n_probes,
-                        probes.data() + (size_t)idx.shard_rank * slice * n_probes, 0, qc.data());
-      shard_allgather_inplace_u32(res, idx.shard_comm, probes.data(), (size_t)slice * n_probes);
-    } else {
-      select_clusters(res, idx, qf.data(), nq, n_probes, probes.data(), p.coarse_search_dtype, qc.data());
-    }
-    rotate_queries(res, idx, qf.data(), qc.data(), nq, p.coarse_search_dtype, rot_q.data());  // ivf_pq_search.cuh:995-1017
-    if (p.coarse_search_dtype != 0 && idx.metric == M_CosineExpanded) normalize_rows(res, rot_q.data(), nq, idx.rot_dim);
-    // list-major grouping of the (query, probe) pairs
-    const uint32_t* labels = probes.data();
-    if (overlap) {  // fork: the helper stream starts behind the probes and the rotated queries
-      pq3_warm(res, idx, true);  // (derived tables of the index: built here, on the handle's stream, if they are not there yet)
-      HIP_TRY(hipEventRecord(res.aux_events[0], res.stream));
-      HIP_TRY(hipStreamWaitEvent(gres.stream, res.aux_events[0], 0));
-      fork_guard.armed = true;
-    }
-    if (head > 0 || sharded) {
-      hipLaunchKernelGGL(phase_labels_kernel, dim3(nblk(n_pairs, 256)), dim3(256), 0, gres.stream, probes.data(),
-                         n_pairs, n_probes, head, idx.n_lists, phase_labels.data(), (uint32_t)idx.shard_world,
-                         (uint32_t)idx.shard_rank, n_ranges, idx.list_owner.data(), head_rows != 0u);
-      labels = phase_labels.data();
-    }
-    // the tail phase (warm bounds) of the common configuration runs pq_scan2_kernel on items of 2 * qpb pairs
-    // (8 pairs whatever the LUT type: two groups of four with an fp16 LUT, four groups of two with an fp32 LUT)
-    bool use2 = head > 0 && bits8 && idx.pq_len == 2 && idx.codebook_kind == 0 && k <= 64 &&  // (k <= 64 excludes the non-fused path)
-                ((lut_half && qpb == 4) || (!lut_half && qpb == 2));
-    use2 = use2 && res.tune.pq_scan2 != 0 && !use3x;
-    // with the matrix-core tail phase the LUT scan only sees the head pairs - nearly always one query per list at the
-    // bench shape (10k queries, 16384 lists) - and the pairs of handed-back queries: single-query items and a
-    // single-query LUT (a quarter of the LUT build and of the accumulate work of the 4-query interleave)
-    const int lut_mode = lut_fp8 ? 2 : (p.lut_dtype != 0 ? 1 : 0);
-    // (the wide path: pq_head_kernel only serves the pairs of handed-back queries, when its LUT fits next to its score keys)
-    const bool head1 = (use3 && !glut) || (usew && !glut && idx.rot_dim <= 256 /* its residual buffers */ && (size_t)idx.pq_dim * 256 * ((p.lut_dtype == 0 || (lut_fp8 && !acc_half)) ? 4 : 2) <= 96 * 1024);
-    build_work_items(gres, labels, n_pairs, n_labels, head1 ? 1 : qpb, sorted_pairs.data(), pair_off.data(), item_off.data(),
-                     items.data(), (int)idx.n_lists, use2 ? 8 : qpb, overlap ? group_scratch.data() : nullptr,
-                     n_ranges /* the shard's bucket of foreign pairs stays as the scatter left it */, n_probes, nq);
-    if (overlap)
-      hipLaunchKernelGGL(head_items_kernel, dim3(nblk(nq, 256)), dim3(256), 0, res.stream, probes.data(), nq, n_probes,
-                         (uint32_t)idx.shard_world, (uint32_t)idx.shard_rank, idx.list_owner.data(), hitems.data(), hpairs.data(),
-                         hpairs.data() + bs_alloc);
-    HIP_TRY(hipMemsetAsync(query_kth.data(), 0xff, (size_t)nq * sizeof(uint32_t), res.stream));
-    HIP_TRY(hipMemsetAsync(tickets.data(), 0, tickets.bytes(), res.stream));
-    // per-pair candidate rows start out invalid: the scan only writes the rows of pairs that found something
-    if (use3x) {
-      // matrix-core tail phase: only the head segments of a query's row are read before they are written (the pool behind
-      // them is filled by count, the rows of handed-back queries are reset by reset_flagged_kernel) - no fill of all
-      // n_pairs x k slots (205 MB per batch at the bench shape; on a list shard most of them belong to foreign pairs)
-      hipLaunchKernelGGL(init_head_rows_kernel, dim3(nblk(nq * (int64_t)head * k, 256)), dim3(256), 0, res.stream, cand_d.data(),
-                         cand_i.data(), nq, (int64_t)n_probes * k, (uint32_t)(head * k));
-    } else if (!large_k) {
-      HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(cand_d.data()), 0x7f7fffff, (size_t)n_pairs * k, res.stream));
-      HIP_TRY(hipMemsetAsync(cand_i.data(), 0xff, (size_t)n_pairs * k * sizeof(uint32_t), res.stream));
-    } else {
-      HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(cand_d.data()), 0x7f7fffff, (size_t)nq * scores_ld, res.stream));
-      HIP_TRY(hipMemsetAsync(cand_i.data(), 0xff, (size_t)nq * scores_ld * sizeof(uint32_t), res.stream));
-      hipLaunchKernelGGL(pair_segments_kernel, dim3(nblk(nq, 256)), dim3(256), 0, res.stream, probes.data(),
-                         idx.list_sizes.data(), nq, n_probes, pair_seg.data());
-    }
-    scan_args a;
-    a.query_kth = query_kth.data();
-    a.items = items.data(); a.sorted_pairs = sorted_pairs.data(); a.n_lists = idx.n_lists;
-    a.rot_queries = rot_q.data(); a.centers_rot = idx.centers_rot.data(); a.pq_centers = idx.pq_centers.data();
-    a.per_cluster = idx.codebook_kind == 1;
-    a.codes = idx.codes.data(); a.list_offsets = idx.list_offsets.data(); a.list_sizes = idx.list_sizes.data();
-    a.out_d = cand_d.data(); a.out_i = cand_i.data();
-    a.all_scores = large_k ? cand_d.data() : nullptr; a.all_rows = cand_i.data(); a.pair_seg = pair_seg.data(); a.scores_ld = scores_ld;
-    a.n_probes = n_probes; a.rot_dim = idx.rot_dim; a.pq_dim = idx.pq_dim; a.pq_len = idx.pq_len;
-    a.pq_bits = idx.pq_bits; a.n_chunks = idx.n_chunks; a.cpc = idx.codes_per_chunk; a.k = (uint32_t)k_scan;
-    a.is_ip = idx.metric == M_InnerProduct || idx.metric == M_CosineExpanded;
-    a.lut_fp8 = lut_fp8 ? 1 : 0;
-    a.dbg   = res.tune.scan_debug;
-    a.qcap  = (uint32_t)std::max(0, res.tune.pq_qcap);
-    a.filter_bits = filter_bits; a.indices = idx.indices.data();
-    const unsigned grid = (unsigned)std::max(8, res.num_cus / 8 * 8);  // persistent: one workgroup per CU
-    dev_buf<unsigned long long> stats(res, (a.dbg & (128 | 512)) ? (size_t)ST_COUNT * grid * kScanWaves : 0);
-    a.stats = stats.data();
-    if (a.dbg & (128 | 512)) HIP_TRY(hipMemsetAsync(stats.data(), 0, stats.bytes(), res.stream));
-    dev_buf<char> glut_buf;
-    if (glut) {
-      const size_t entry = 8;  // 4 x fp16 or 2 x fp32
-      a.global_lut_stride = ((size_t)idx.pq_dim * idx.pq_book * entry + 255) & ~size_t(255);
-      glut_buf     = dev_buf<char>(res, a.global_lut_stride * grid);
-      a.global_lut = glut_buf.data();
-    }
-    auto launch = [&](const scan_args& sa) {
-      if (glut) {
-        if (!lut_half)      launch_scan_glut<float, float, 2>(res, sa, smem, grid, big_k);
-        else if (!acc_half) launch_scan_glut<__half, float, 4>(res, sa, smem, grid, big_k);
-        else                launch_scan_glut<__half, __half, 4>(res, sa, smem, grid, big_k);
-        return;
-      }
-      if (!lut_half) {
-        if (qpb == 2) launch_scan_qpb<float, float, 2>(res, sa, smem, grid, bits8, big_k);
-        else          launch_scan_qpb<float, float, 1>(res, sa, smem, grid, bits8, big_k);
-      } else if (!acc_half) {
-        if (qpb == 4)      launch_scan_qpb<__half, float, 4>(res, sa, smem, grid, bits8, big_k);
-        else if (qpb == 2) launch_scan_qpb<__half, float, 2>(res, sa, smem, grid, bits8, big_k);
-        else               launch_scan_qpb<__half, float, 1>(res, sa, smem, grid, bits8, big_k);
-      } else {
-        if (qpb == 4)      launch_scan_qpb<__half, __half, 4>(res, sa, smem, grid, bits8, big_k);
-        else if (qpb == 2) launch_scan_qpb<__half, __half, 2>(res, sa, smem, grid, bits8, big_k);
-        else               launch_scan_qpb<__half, __half, 1>(res, sa, smem, grid, bits8, big_k);
-      }
-    };
-    auto launch1 = [&](const scan_args& sa) {  // single-pair work items: scores of the whole list in LDS, k smallest selected there
-      pq3_head h{};
-      h.items = sa.items; h.item_begin = sa.item_begin; h.item_end = sa.item_end; h.xcd_ticket = sa.xcd_ticket;
-      h.sorted_pairs = sa.sorted_pairs; h.rot_queries = sa.rot_queries; h.cand_d = sa.out_d; h.cand_i = sa.out_i;
-      h.query_kth = sa.query_kth; h.n_probes = n_probes; h.k = (uint32_t)k; h.max_list_len = max_list_len; h.is_ip = sa.is_ip;
-      h.lut_mode = lut_mode; h.acc_half = acc_half ? 1 : 0; h.filter_bits = filter_bits;
-      h.one_shot = sa.one_shot; h.row_limit = sa.row_limit;
-      dev_buf<unsigned long long> hst(res, (sa.dbg & 2048) ? 8 : 0);
-      if (sa.dbg & 2048) HIP_TRY(hipMemsetAsync(hst.data(), 0, hst.bytes(), res.stream));
-      h.stats = hst.data();
-      pq3_head_scan(res, idx, h);
-      if (sa.dbg & 2048) {
-        auto hs = to_host(res, hst.data(), 8);
-        const double n = (double)std::max<unsigned long long>(1, hs[5]);
-        fprintf(stderr, "[pq_head] items %llu; workgroup cycles per item: header %.0f, LUT %.0f, scores %.0f, select %.0f, output %.0f\n", hs[5],
-                hs[0] / n, hs[1] / n, hs[2] / n, hs[3] / n, hs[4] / n);
-      }
-    };
-    if (head > 0) {
-      a.xcd_ticket = tickets.data();
-      a.item_begin = nullptr;                        a.item_end = item_off.data() + idx.n_lists;
-      if (usew) {
-        // the wide path's head phase is a bound-only pass through the filter: below, with the tail phase's run description
-      } else if (overlap) {  // head phase straight from the probes (one single-pair item per query), no grouping in its way
-        scan_args ah = a;
-        ah.items = hitems.data(); ah.sorted_pairs = hpairs.data(); ah.item_end = hpairs.data() + bs_alloc;
-        ah.one_shot = (uint32_t)nq;  // one workgroup per item: slots free up item by item, the helper stream's kernels fit in between
-        ah.row_limit = head_rows;
-        launch1(ah);
-      } else if (head1) launch1(a); else launch(a);  // head phase: the nearest probes, cold bounds
-      // list-sharded index with a communicator: every rank continues with the bound of the query's globally nearest
-      // probe (one all-reduce of nq keys), not only the rank that owns that probe
-      if (idx.shard_comm != nullptr) shard_allreduce_min_u32(res, idx.shard_comm, query_kth.data(), (size_t)nq);
-      a.xcd_ticket = tickets.data() + 8 * 32;
-      a.item_begin = item_off.data() + idx.n_lists;  a.item_end = item_off.data() + 2 * idx.n_lists;
-      if (use3x) {
-        HIP_TRY(hipMemsetAsync(qstate.data(), 0, qstate.bytes(), res.stream));
-        pq3_run r{};
-        r.pair_norms = pair_norms.data(); r.head_rows = head_rows;
-        r.nq = nq; r.n_probes = n_probes; r.k = (uint32_t)k; r.head = head; r.is_ip = a.is_ip;
-        r.lut_mode = lut_fp8 ? 2 : (p.lut_dtype != 0 ? 1 : 0); r.acc_half = acc_half ? 1 : 0;
-        r.sorted_pairs = sorted_pairs.data(); r.pair_off = pair_off.data(); r.probes = probes.data();
-        r.rot_queries = rot_q.data(); r.query_kth = query_kth.data();
-        r.cand_d = cand_d.data(); r.cand_i = cand_i.data(); r.cand_r = cand_r.data();
-        r.qflag = qstate.data(); r.qcnt = qstate.data() + bs_alloc; r.counters = qstate.data() + 2 * bs_alloc;
-        r.surv_cnt = qstate.data() + 2 * bs_alloc + 2;
-        r.ov_cnt = qstate.data() + 2 * bs_alloc + 4 + pq3_regions(res); r.ov_off = r.ov_cnt + bs_alloc;
-        r.surv = surv.data(); r.surv_cap = surv_cap; r.units = units3.data(); r.unit_off = unit_off.data();
-        r.unit_rows = unit_rows; r.xcd_ticket = tickets.data() + 2 * 8 * 32; r.fb_items = fb_items.data();
-        r.filter_bits = filter_bits; r.overflow = overflow3.data(); r.overflow_cap = overflow_cap;
-        r.bq = (use_f4 || usew) ? bq3.data() : nullptr; r.thr = thr3.data();
-        dev_buf<unsigned long long> st3(res, (a.dbg & 1024) ? 8 : 0);
-        if (a.dbg & 1024) HIP_TRY(hipMemsetAsync(st3.data(), 0, st3.bytes(), res.stream));
-        r.stats = st3.data(); r.filter_dbg = (a.dbg >> 16) & 255;  // CUVS_AMD_SCAN_DEBUG bits 16..23
-        if (overlap) {
-          // the helper stream: work units, B operands and norms of the tail pairs (nothing here reads the head phase's bounds);
-          // join; then thresholds, filter and re-score behind the head kernel (and the bound all-reduce) on the handle's stream
-          r.stage = 1;
-          pq3_tail(gres, idx, r);
-          HIP_TRY(hipEventRecord(res.aux_events[1], gres.stream));
-          HIP_TRY(hipStreamWaitEvent(res.stream, res.aux_events[1], 0));
-          fork_guard.armed = false;  // joined: everything the helper stream was given is ordered before the handle's stream again
-          r.stage = 2;
-        }
-        if (usew) {
-          const pqw_bufs hb{w_x.data(), w_ldx, w_kv.data(), w_ki.data(), w_thr.data(), w_c.data(), w_nm.data(), tickets.data(), w_blk.data(), w_bt.data()};
-          const bool ok = pqw_head_bounds(res, idx, r, hb);
-          CUVS_EXPECTS(ok, "ivf_pq: the wide path's decoded rows are gone");
-          pqw_tail(res, idx, r, hb);
-        } else {
-          pq3_tail(res, idx, r);
-        }
-        // queries the filter could not serve (no finite bound, operands beyond fp16, full pool): LUT scan of their pairs
-        a.items = fb_items.data(); a.item_begin = nullptr; a.item_end = r.counters;
-        a.xcd_ticket = tickets.data() + 3 * 8 * 32;
-        if (head1) launch1(a); else launch(a);
-        pq3_merge(res, r, top_d.data(), top_i.data());
-        if (a.dbg & 1024) {
-          auto hs = to_host(res, st3.data(), 8);
-          g_pq3_last_stats[0] = hs[0]; g_pq3_last_stats[1] = hs[1]; g_pq3_last_stats[2] = hs[2]; g_pq3_last_stats[3] = hs[7];
-          fprintf(stderr, "[pq_scan3] units %llu; wave cycles per unit: prologue %.0f, loop %.0f (slow path %.0f); per subtile %.0f\n", hs[7],
-                  (double)hs[4] / std::max<unsigned long long>(1, hs[7]), (double)hs[5] / std::max<unsigned long long>(1, hs[7]),
-                  (double)hs[6] / std::max<unsigned long long>(1, hs[7]), (double)hs[5] / std::max<unsigned long long>(1, hs[2]));
-          auto hc = to_host(res, r.counters, 2);
-          g_pq3_last_stats[4] = hc[0]; g_pq3_last_stats[5] = hc[1];
-          fprintf(stderr, "[pq_scan3] overflow entries %u\n", hc[1]);
-          hc[1] = hc[0];
-          fprintf(stderr, "[pq_scan3] pairs screened %llu, survivors %llu (%.4f%%), subtiles %llu (slow path %llu), fallback pairs %u\n",
-                  hs[0], hs[1], 100.0 * hs[1] / (double)std::max<unsigned long long>(1, hs[0]), hs[2], hs[3], hc[1]);
-        }
-      }
-      else if (!use2)     launch(a);  // tail phase: warm bounds
-      else if (!lut_half) launch_scan2<float, float, 2, 4>(res, a, grid);
-      else if (!acc_half) launch_scan2<__half, float, 4, 2>(res, a, grid);
-      else                launch_scan2<__half, __half, 4, 2>(res, a, grid);
-    } else {
-      a.xcd_ticket = tickets.data();
-      a.item_begin = nullptr; a.item_end = item_off.data() + idx.n_lists;
-      launch(a);
-    }
-    if (a.dbg & (128 | 512)) {
-      std::vector<unsigned long long> hw(stats.n);
-      HIP_TRY(hipMemcpyAsync(hw.data(), stats.data(), stats.bytes(), hipMemcpyDeviceToHost, res.stream));
-      HIP_TRY(hipStreamSynchronize(res.stream));
-      unsigned long long h[ST_COUNT] = {};
-      for (size_t i = 0; i < hw.size(); ++i) h[i % ST_COUNT] += hw[i];
-      const double w = 1.0 / (16.0 * grid);  // wave cycles -> average cycles per wave
-      if (a.dbg & 4096) {  // per-wave view of the filter pass (which wave of a workgroup runs late?)
-        for (int which : {(int)ST_SCAN, (int)ST_ALIVE2, (int)ST_F_GATHER, (int)ST_F_FLUSH, (int)ST_STAGE2, (int)ST_CAND, (int)ST_S2_CALLS}) {
-          fprintf(stderr, "[pq_scan per-wave stat %d, Mcycles]", which);
-          for (int wv = 0; wv < kScanWaves; ++wv) {
-            unsigned long long t = 0;
-            for (unsigned b = 0; b < grid; ++b) t += hw[((size_t)b * kScanWaves + wv) * ST_COUNT + which];
-            fprintf(stderr, " %.2f", (double)t / grid * 1e-6);
-          }
-          fprintf(stderr, "\n");
-        }
-      }
-      fprintf(stderr,
-              "[pq_scan stats] items %llu rows %llu queued %llu (%.2f%%) stage2 calls %llu alive after chunk1/2/3 %llu/%llu/%llu"
-              " | cycles per wave: header %.3g lut %.3g scan %.3g (stage2 %.3g) merge+sync %.3g\n",
-              h[ST_ITEMS], h[ST_ROWS], h[ST_QUEUED], 100.0 * h[ST_QUEUED] / (double)std::max<unsigned long long>(1, h[ST_ROWS]),
-              h[ST_S2_CALLS], h[ST_ALIVE1], h[ST_ALIVE2], h[ST_ALIVE3], h[ST_HEADER] * w, h[ST_LUT] * w, h[ST_SCAN] * w,
-              h[ST_STAGE2] * w, (double)(h[ST_MERGE] - h[ST_HEADER] - h[ST_LUT] - h[ST_SCAN]) * w);
-      fprintf(stderr, "[pq_scan2 waits, cycles per wave] after filter LUT %.3g, after filter pass %.3g, before LUT B %.3g, after exact LUT "
-              "%.3g, after exact pass %.3g, merge %.3g | filter pass: code-load wait %.3g, gather block %.3g, flush %.3g\n",
-              h[ST_ALIVE1] * w, h[ST_ALIVE2] * w, h[ST_S2_CALLS] * w, h[ST_ALIVE3] * w, h[ST_CAND] * w, h[ST_MERGE] * w,
-              h[ST_F_LOAD] * w, h[ST_F_GATHER] * w, h[ST_F_FLUSH] * w);
-    }
-    // per-query merge of n_probes * k candidates (ivf_pq_search.cuh:646-655)
-    if (use3x) {
-      // merged already (pq3_merge: head lists + pool)
-    } else if (!large_k) {
-      select_k<uint32_t, uint32_t>(res, cand_d.data(), cand_i.data(), nq, (int64_t)n_probes * k, (int64_t)n_probes * k,
-                                   k, top_d.data(), top_i.data(), true);
-    } else {
-      select_k<uint32_t, uint32_t>(res, cand_d.data(), cand_i.data(), nq, (int64_t)scores_ld, (int64_t)scores_ld, k,
-                                   top_d.data(), top_i.data(), true);
-    }
-    const float sc = ivf_pq_index::scale(et);
-    hipLaunchKernelGGL(postprocess_kernel, dim3(nblk(nq * k, 256)), dim3(256), 0, res.stream, top_i.data(),
-                       top_d.data(), nq * k, idx.indices.data(), idx.metric, sc * sc, neighbors + q0 * k,
-                       distances + q0 * k);
-  }
+  aux_fork_guard fork_guard;  // (after the scratch: see aux_fork_guard)
+  fork_guard.s = pl.overlap ? aux.stream : nullptr;
+  const pq_search_ctx c{res, pl.overlap ? aux : res, p, idx, pl, scratch, fork_guard, k, filter_bits};
+  for (int64_t q0 = 0; q0 < n_queries; q0 += pl.max_batch)
+    pq_search_batch(c, queries, et, q0, std::min(pl.max_batch, n_queries - q0), neighbors, distances);
   HIP_TRY(hipGetLastError());
 }
 
 }  // namespace cuvs_amd
+
+// Test hook (not part of the reference ABI): the search plan for given parameters, computed on the host without
+// touching a GPU - tests pin it to the dispatch rules of ivf_pq_search (tests/test_ivf_pq_plan_cpu.py). The index is a
+// host-only shell of the given shape and list sizes (shard_world > 1: a list shard without a communicator); the tuning
+// is the production one. out: path, glut, head1, overlap, big_k, filter4, qpb, smem, k_scan, head, wheads, head_rows,
+// max_list_len, w_ldx, n_ranges, n_labels, max_batch, bs_alloc, surv_cap, overflow_cap, max_units, unit_rows, max_items,
+// shard_coarse.
+extern "C" __attribute__((visibility("default"))) int cuvsAmdIvfPqSearchPlan(
+  uint32_t dim, uint32_t rot_dim, uint32_t pq_dim, uint32_t pq_len, uint32_t pq_bits, uint32_t shard_world, int codebook_kind,
+  int metric, uint32_t n_lists, const uint32_t* list_sizes, cuvsIvfPqSearchParams_t params, int k, int64_t n_queries, int num_cus,
+  uint64_t batch_limit_bytes, int wide_rows_ready, int64_t out[24])
+{
+  return cuvs_amd::translate_exceptions([=] {
+    using namespace cuvs_amd;
+    CUVS_EXPECTS(params != nullptr && list_sizes != nullptr && n_lists > 0 && pq_bits >= 4 && pq_bits <= 8, "invalid argument");
+    ivf_pq_index idx;
+    idx.metric = metric; idx.codebook_kind = codebook_kind; idx.n_lists = n_lists; idx.dim = dim; idx.rot_dim = rot_dim;
+    idx.pq_dim = pq_dim; idx.pq_len = pq_len; idx.pq_bits = pq_bits; idx.pq_book = 1u << pq_bits;
+    idx.codes_per_chunk = 128 / pq_bits; idx.n_chunks = (uint32_t)ceil_div(pq_dim, idx.codes_per_chunk);
+    idx.shard_world = (int)std::max(1u, shard_world);
+    idx.h_list_sizes.assign(list_sizes, list_sizes + n_lists);
+    for (uint32_t v : idx.h_list_sizes) idx.size += v;
+    ivf_pq_search_params sp;
+    sp.n_probes = params->n_probes; sp.lut_dtype = (int)params->lut_dtype; sp.internal_distance_dtype = (int)params->internal_distance_dtype;
+    sp.coarse_search_dtype = (int)params->coarse_search_dtype; sp.max_internal_batch_size = params->max_internal_batch_size;
+    const size_t largest_total = k > 256 ? largest_lists_total(idx.h_list_sizes, std::min<uint32_t>(sp.n_probes, n_lists)) : 0;
+    const pq_search_plan pl = make_pq_search_plan(idx, sp, k, n_queries, tuning{}, num_cus, (size_t)batch_limit_bytes, largest_total,
+                                                  [=] { return wide_rows_ready != 0; });
+    const int64_t v[24] = {(int64_t)pl.path, pl.glut, pl.head1, pl.overlap, pl.big_k, pl.filter4, pl.qpb, (int64_t)pl.smem, pl.k_scan,
+                           pl.head, pl.wheads, pl.head_rows, pl.max_list_len, pl.w_ldx, pl.n_ranges, pl.n_labels, pl.max_batch,
+                           pl.bs_alloc, pl.surv_cap, pl.overflow_cap, (int64_t)pl.max_units, pl.unit_rows, pl.max_items,
+                           pl.shard_coarse};
+    std::copy(v, v + 24, out);
+  });
+}
