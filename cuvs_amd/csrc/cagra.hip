@@ -545,6 +545,68 @@ __device__ inline uint32_t team_distances(const T* __restrict__ data, int64_t di
   return n_scored;
 }
 
+// BitwiseHamming distances of the nodes idx[first .. first+count) to the query (uint8 / int8 rows, compared as bytes): the same
+// 8 teams of 8 lanes and 16-byte pieces as team_distances; lane t XORs its pieces with the query's (staged in LDS as bytes)
+// and counts the set bits, the 8 counts are summed by the xor butterfly. The count is the distance (exact in fp32).
+__device__ inline uint32_t team_hamming(const uint8_t* __restrict__ data, int64_t dim, const uint8_t* __restrict__ qb,
+                                        uint32_t* __restrict__ keys, const uint32_t* __restrict__ idx, uint32_t first,
+                                        uint32_t count, int lane)
+{
+  const int team = lane >> 3, tl = lane & 7;
+  const bool vec = (dim % 16 == 0) && ((reinterpret_cast<uintptr_t>(data) & 15) == 0);
+  auto bits = [](const uint4& w, const uint4& q) {
+    return (uint32_t)(__popc(w.x ^ q.x) + __popc(w.y ^ q.y) + __popc(w.z ^ q.z) + __popc(w.w ^ q.w));
+  };
+  uint32_t n_scored = 0u;
+  for (uint32_t c0 = 0; c0 < count; c0 += 8) {
+    const uint32_t c    = c0 + team;
+    const uint32_t node = c < count ? (idx[first + c] & ~kParentFlag) : kInvalidNode;
+    const bool ok       = c < count && idx[first + c] != kInvalidNode;
+    n_scored += (uint32_t)__popcll(__ballot(ok && tl == 0));
+    uint32_t cnt = 0u;
+    if (ok) {
+      const uint8_t* row = data + (int64_t)node * dim;
+      int64_t d0         = (int64_t)tl * 16;
+      if (vec) {
+        // four 16-byte pieces in flight per lane, as in team_distances
+        for (; d0 + 3 * 128 < dim; d0 += 4 * 128) {
+          const uint4 w0 = *reinterpret_cast<const uint4*>(row + d0);
+          const uint4 w1 = *reinterpret_cast<const uint4*>(row + d0 + 128);
+          const uint4 w2 = *reinterpret_cast<const uint4*>(row + d0 + 256);
+          const uint4 w3 = *reinterpret_cast<const uint4*>(row + d0 + 384);
+          cnt += bits(w0, *reinterpret_cast<const uint4*>(qb + d0)) + bits(w1, *reinterpret_cast<const uint4*>(qb + d0 + 128)) +
+                 bits(w2, *reinterpret_cast<const uint4*>(qb + d0 + 256)) + bits(w3, *reinterpret_cast<const uint4*>(qb + d0 + 384));
+        }
+        for (; d0 < dim; d0 += 128)
+          cnt += bits(*reinterpret_cast<const uint4*>(row + d0), *reinterpret_cast<const uint4*>(qb + d0));
+      } else {  // byte tail: the 16 bytes of a piece are loaded first (clamped index, no branch), then counted
+        for (; d0 < dim; d0 += 128) {
+          uint32_t w[16];
+#pragma unroll
+          for (int e = 0; e < 16; ++e) {
+            const int64_t d = min(d0 + e, dim - 1);
+            w[e]            = (uint32_t)(row[d] ^ qb[d]);
+          }
+#pragma unroll
+          for (int e = 0; e < 16; ++e) cnt += d0 + e < dim ? (uint32_t)__popc(w[e]) : 0u;
+        }
+      }
+    }
+    cnt += (uint32_t)__shfl_xor((int)cnt, 1, kWave);
+    cnt += (uint32_t)__shfl_xor((int)cnt, 2, kWave);
+    cnt += (uint32_t)__shfl_xor((int)cnt, 4, kWave);
+    if (tl == 0 && c < count) keys[first + c] = ok ? float_to_key((float)cnt) : 0xffffffffu;
+  }
+  return n_scored;
+}
+
+// 32-bit words of LDS that hold the query: fp32 elements, or (BitwiseHamming) bytes padded to 16
+template <bool HAM>
+__host__ __device__ inline int64_t query_words(int64_t dim)
+{
+  return HAM ? ((dim + 15) & ~int64_t(15)) / 4 : ((dim + 3) & ~int64_t(3));
+}
+
 __device__ inline float wave_query_norm(const float* qf, int64_t dim, int lane)
 {
   float s = 0.f;
@@ -554,20 +616,26 @@ __device__ inline float wave_query_norm(const float* qf, int64_t dim, int lane)
   return sqrtf(s);
 }
 
-template <typename T>
+// HAM: BitwiseHamming over the bytes of uint8 / int8 rows (T = uint8_t), the query staged as bytes
+template <typename T, bool HAM = false>
 __global__ __launch_bounds__(64) void cagra_search_kernel(search_args a)
 {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane   = threadIdx.x;
   const int64_t qi = blockIdx.x;
   float* qf        = reinterpret_cast<float*>(smem);
-  uint32_t* keys   = reinterpret_cast<uint32_t*>(qf + ((a.dim + 3) & ~int64_t(3)));
+  uint8_t* qb      = reinterpret_cast<uint8_t*>(smem);
+  uint32_t* keys   = reinterpret_cast<uint32_t*>(smem) + query_words<HAM>(a.dim);
   uint32_t* idx    = keys + a.np2;
   uint32_t* table  = idx + a.np2;
   const uint32_t hsize = 1u << a.hash_bits;
   const T* data    = static_cast<const T*>(a.data);
 
-  for (int64_t d = lane; d < a.dim; d += 64) qf[d] = to_float(static_cast<const T*>(a.queries)[qi * a.dim + d]);
+  if constexpr (HAM) {
+    for (int64_t d = lane; d < a.dim; d += 64) qb[d] = static_cast<const uint8_t*>(a.queries)[qi * a.dim + d];
+  } else {
+    for (int64_t d = lane; d < a.dim; d += 64) qf[d] = to_float(static_cast<const T*>(a.queries)[qi * a.dim + d]);
+  }
   for (uint32_t i = lane; i < a.np2; i += 64) { keys[i] = 0xffffffffu; idx[i] = kInvalidNode; }
   for (uint32_t i = lane; i < hsize; i += 64) table[i] = kInvalidNode;
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -593,7 +661,8 @@ __global__ __launch_bounds__(64) void cagra_search_kernel(search_args a)
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    n_dist += team_distances<T>(data, a.dim, qf, tkeys, tidx, 0, n_seed, a.is_ip, lane, a.norms, qn);
+    if constexpr (HAM) n_dist += team_hamming(reinterpret_cast<const uint8_t*>(data), a.dim, qb, tkeys, tidx, 0, n_seed, lane);
+    else               n_dist += team_distances<T>(data, a.dim, qf, tkeys, tidx, 0, n_seed, a.is_ip, lane, a.norms, qn);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
     for (uint32_t i = lane; i < n_seed; i += 64)
@@ -653,7 +722,8 @@ __global__ __launch_bounds__(64) void cagra_search_kernel(search_args a)
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    n_dist += team_distances<T>(data, a.dim, qf, keys, idx, a.itopk, n_cand, a.is_ip, lane, a.norms, qn);
+    if constexpr (HAM) n_dist += team_hamming(reinterpret_cast<const uint8_t*>(data), a.dim, qb, keys, idx, a.itopk, n_cand, lane);
+    else               n_dist += team_distances<T>(data, a.dim, qf, keys, idx, a.itopk, n_cand, a.is_ip, lane, a.norms, qn);
     n_rows_read += n_parents;
     ++iter;
   }
@@ -742,7 +812,7 @@ __device__ inline void trav_remove(uint32_t* table, uint32_t bits, uint32_t key)
   }
 }
 
-template <typename T>
+template <typename T, bool HAM = false>
 __global__ __launch_bounds__(1024) void cagra_search_multi_kernel(mw_args m)
 {
   const search_args& a = m.s;
@@ -752,7 +822,8 @@ __global__ __launch_bounds__(1024) void cagra_search_multi_kernel(mw_args m)
   const int64_t qi = blockIdx.x;
   const uint32_t W = m.n_waves, np2 = m.np2_local, vsize = 1u << m.vis_bits, tsize = 1u << m.trav_bits;
   float* qf        = reinterpret_cast<float*>(smem);
-  uint32_t* trav   = reinterpret_cast<uint32_t*>(qf + ((a.dim + 3) & ~int64_t(3)));
+  uint8_t* qb      = reinterpret_cast<uint8_t*>(smem);
+  uint32_t* trav   = reinterpret_cast<uint32_t*>(smem) + query_words<HAM>(a.dim);
   uint32_t* mkeys  = trav + tsize;             // merge area [merge_np2]
   uint32_t* midx   = mkeys + m.merge_np2;
   uint32_t* wbase  = midx + m.merge_np2 + (size_t)wave * (2 * np2 + vsize);
@@ -762,7 +833,11 @@ __global__ __launch_bounds__(1024) void cagra_search_multi_kernel(mw_args m)
   uint32_t* vis    = idx + np2;                // this wave's visited table (rebuilt every iteration)
   const T* data    = static_cast<const T*>(a.data);
 
-  for (int64_t d = threadIdx.x; d < a.dim; d += blockDim.x) qf[d] = to_float(static_cast<const T*>(a.queries)[qi * a.dim + d]);
+  if constexpr (HAM) {
+    for (int64_t d = threadIdx.x; d < a.dim; d += blockDim.x) qb[d] = static_cast<const uint8_t*>(a.queries)[qi * a.dim + d];
+  } else {
+    for (int64_t d = threadIdx.x; d < a.dim; d += blockDim.x) qf[d] = to_float(static_cast<const T*>(a.queries)[qi * a.dim + d]);
+  }
   for (uint32_t i = threadIdx.x; i < tsize; i += blockDim.x) trav[i] = kInvalidNode;
   for (uint32_t i = lane; i < np2; i += 64) { keys[i] = 0xffffffffu; idx[i] = kInvalidNode; }
   for (uint32_t i = lane; i < vsize; i += 64) vis[i] = kInvalidNode;
@@ -785,7 +860,8 @@ __global__ __launch_bounds__(1024) void cagra_search_multi_kernel(mw_args m)
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       __builtin_amdgcn_wave_barrier();
-      n_dist += team_distances<T>(data, a.dim, qf, tkeys, tidx, 0, n_seed, a.is_ip, lane, a.norms, qn);
+      if constexpr (HAM) n_dist += team_hamming(reinterpret_cast<const uint8_t*>(data), a.dim, qb, tkeys, tidx, 0, n_seed, lane);
+      else               n_dist += team_distances<T>(data, a.dim, qf, tkeys, tidx, 0, n_seed, a.is_ip, lane, a.norms, qn);
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       __builtin_amdgcn_wave_barrier();
       for (uint32_t i = lane; i < n_seed; i += 64)
@@ -875,7 +951,8 @@ __global__ __launch_bounds__(1024) void cagra_search_multi_kernel(mw_args m)
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    n_dist += team_distances<T>(data, a.dim, qf, keys, idx, kMwTopk, a.degree, a.is_ip, lane, a.norms, qn);
+    if constexpr (HAM) n_dist += team_hamming(reinterpret_cast<const uint8_t*>(data), a.dim, qb, keys, idx, kMwTopk, a.degree, lane);
+    else               n_dist += team_distances<T>(data, a.dim, qf, keys, idx, kMwTopk, a.degree, a.is_ip, lane, a.norms, qn);
     n_rows_read += parent != kInvalidNode ? 1u : 0u;
     // ---- drop what another wave has expanded meanwhile; a parent that fails the filter leaves the list
     for (uint32_t i = lane; i < np2; i += 64) {
@@ -927,10 +1004,10 @@ __global__ __launch_bounds__(1024) void cagra_search_multi_kernel(mw_args m)
   }
 }
 
-template <typename T>
+template <typename T, bool HAM = false>
 void launch_search_multi(resources& res, const mw_args& m, int64_t nq, size_t smem)
 {
-  auto kern = cagra_search_multi_kernel<T>;
+  auto kern = cagra_search_multi_kernel<T, HAM>;
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
   profile_begin(res, "cagra_search_multi_kernel");
   hipLaunchKernelGGL(kern, dim3((unsigned)nq), dim3(64 * m.n_waves), smem, res.stream, m);
@@ -938,10 +1015,10 @@ void launch_search_multi(resources& res, const mw_args& m, int64_t nq, size_t sm
   HIP_TRY(hipGetLastError());
 }
 
-template <typename T>
+template <typename T, bool HAM = false>
 void launch_search(resources& res, const search_args& a, int64_t nq, size_t smem)
 {
-  auto kern = cagra_search_kernel<T>;
+  auto kern = cagra_search_kernel<T, HAM>;
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
   profile_begin(res, "cagra_search_kernel");
   hipLaunchKernelGGL(kern, dim3((unsigned)nq), dim3(64), smem, res.stream, a);
@@ -1120,7 +1197,13 @@ void cagra_search(resources& res, const cagra_index& idx, const cuvsCagraSearchP
   a.hash_bits      = bits;
   a.reset_interval = std::max<uint32_t>(1, ((1u << bits) / 2 - itopk) / (a.width * idx.degree));
   a.rand_xor_mask  = p.rand_xor_mask;
-  a.is_ip          = idx.metric == M_InnerProduct ? 1 : (idx.metric == M_CosineExpanded ? 2 : 0);
+  // BitwiseHamming walks its own instantiation of the kernels (popcounts over the row bytes); every other metric keeps the
+  // L2 / inner product / cosine arithmetic it always had
+  const bool ham = idx.metric == M_BitwiseHamming;
+  CUVS_EXPECTS(!ham || idx.dtype == elem_t::u8 || idx.dtype == elem_t::i8,
+               "BitwiseHamming distance is only supported for int8_t and uint8_t data types. Current data type is not supported.");
+  const size_t q_bytes = (size_t)(ham ? query_words<true>(idx.dim) : query_words<false>(idx.dim)) * 4;
+  a.is_ip          = ham ? 3 : (idx.metric == M_InnerProduct ? 1 : (idx.metric == M_CosineExpanded ? 2 : 0));
   a.norms          = idx.norms.data();
   a.work           = res.cagra_work;
   CUVS_EXPECTS(a.is_ip != 2 || a.norms != nullptr, "cagra::search: cosine index without dataset norms");
@@ -1158,28 +1241,36 @@ void cagra_search(resources& res, const cagra_index& idx, const cuvsCagraSearchP
     m.trav_bits  = 11;  // every wave claims <= max_iter parents and inserts <= 32 results; keep the fill <= 50 %
     while ((1u << m.trav_bits) < 2 * W * (m.s.max_iter + kMwTopk)) ++m.trav_bits;
     m.merge_np2 = (uint32_t)next_pow2((int)(W * kMwTopk));
-    size_t msmem = (size_t)((idx.dim + 3) & ~int64_t(3)) * 4 + ((size_t)4 << m.trav_bits) + (size_t)m.merge_np2 * 8 +
+    size_t msmem = q_bytes + ((size_t)4 << m.trav_bits) + (size_t)m.merge_np2 * 8 +
                    (size_t)W * (2 * m.np2_local + (1u << m.vis_bits)) * 4 + (size_t)W * 2 * idx.degree * 4;
     CUVS_EXPECTS(msmem <= 160 * 1024, "cagra::search: dim too large for the multi-wave LDS layout");
-    switch (idx.dtype) {
-      case elem_t::f32: launch_search_multi<float>(res, m, nq, msmem); break;
-      case elem_t::f16: launch_search_multi<__half>(res, m, nq, msmem); break;
-      case elem_t::i8: launch_search_multi<int8_t>(res, m, nq, msmem); break;
-      case elem_t::u8: launch_search_multi<uint8_t>(res, m, nq, msmem); break;
+    if (ham) {
+      launch_search_multi<uint8_t, true>(res, m, nq, msmem);
+    } else {
+      switch (idx.dtype) {
+        case elem_t::f32: launch_search_multi<float>(res, m, nq, msmem); break;
+        case elem_t::f16: launch_search_multi<__half>(res, m, nq, msmem); break;
+        case elem_t::i8: launch_search_multi<int8_t>(res, m, nq, msmem); break;
+        case elem_t::u8: launch_search_multi<uint8_t>(res, m, nq, msmem); break;
+      }
     }
     if (idx.source_indices.data() != nullptr)
       hipLaunchKernelGGL(cagra_source_ids_kernel, dim3((unsigned)grid_blocks(nq * k, 256)), dim3(256), 0, res.stream, out_idx, nq * (int64_t)k,
                          idx64 ? 1 : 0, idx.source_indices.data(), idx.n);
     return;
   }
-  size_t smem = (size_t)((idx.dim + 3) & ~int64_t(3)) * 4 + (size_t)a.np2 * 8 + ((size_t)4 << bits) +
+  size_t smem = q_bytes + (size_t)a.np2 * 8 + ((size_t)4 << bits) +
                 (size_t)(2 * (itopk + a.width * idx.degree) + a.width) * 4;  // + seed candidates, parent list
   CUVS_EXPECTS(smem <= 160 * 1024, "cagra::search: dim/itopk too large for LDS");
-  switch (idx.dtype) {
-    case elem_t::f32: launch_search<float>(res, a, nq, smem); break;
-    case elem_t::f16: launch_search<__half>(res, a, nq, smem); break;
-    case elem_t::i8: launch_search<int8_t>(res, a, nq, smem); break;
-    case elem_t::u8: launch_search<uint8_t>(res, a, nq, smem); break;
+  if (ham) {
+    launch_search<uint8_t, true>(res, a, nq, smem);
+  } else {
+    switch (idx.dtype) {
+      case elem_t::f32: launch_search<float>(res, a, nq, smem); break;
+      case elem_t::f16: launch_search<__half>(res, a, nq, smem); break;
+      case elem_t::i8: launch_search<int8_t>(res, a, nq, smem); break;
+      case elem_t::u8: launch_search<uint8_t>(res, a, nq, smem); break;
+    }
   }
   if (idx.source_indices.data() != nullptr)
     hipLaunchKernelGGL(cagra_source_ids_kernel, dim3((unsigned)grid_blocks(nq * k, 256)), dim3(256), 0, res.stream, out_idx, nq * (int64_t)k,
@@ -1255,12 +1346,81 @@ void cagra_extend(resources& res, cagra_index& idx, const void* new_rows, bool n
   sync(res);
 }
 
+// rows of bytes -> [n, 8 dim] floats of their bits (bit j of byte b -> column 8 b + j): squared L2 over them is the Hamming
+// distance, and every product and partial sum of a float GEMM over 0/1 values is a small integer, so it is exact. Grid-stride:
+// n x 8 dim elements may exceed what one launch of one element per thread can address
+__global__ void expand_bits_kernel(const uint8_t* __restrict__ in, int64_t n_bytes, float* __restrict__ out)
+{
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_bytes * 8; i += (int64_t)gridDim.x * blockDim.x)
+    out[i] = (float)((in[i >> 3] >> (i & 7)) & 1u);
+}
+
+// the kNN graph [n, K] the CAGRA graph is optimised from, by build algorithm (idx: metric, rows, dtype; cosine norms are set
+// for NN-descent)
+void cagra_knn_graph(resources& res, const cuvsCagraIndexParams& p, cagra_index& idx, uint32_t K, uint32_t* knn)
+{
+  const int metric = idx.metric;
+  const elem_t et  = idx.dtype;
+  const int64_t n = idx.n, dim = idx.dim;
+  const bool small = n <= 200000 || p.build_algo == ITERATIVE_CAGRA_SEARCH;
+  if (metric == M_BitwiseHamming) {
+    // NN_DESCENT, or AUTO above 200000 rows (the reference's pick, cagra_build.cuh:2208-2219); otherwise the exact graph
+    // over the rows expanded to 0/1 floats (this library's stand-in for ITERATIVE_CAGRA_SEARCH)
+    if (p.build_algo == NN_DESCENT || !small) {
+      knn_graph_nn_descent(res, idx.data, et, n, dim, K, metric, nullptr, (int)p.nn_descent_niter, knn);
+    } else {
+      // (scratch: n x 32 dim bytes for the expanded rows)
+      dev_buf<float> f(res, (size_t)n * dim * 8);
+      hipLaunchKernelGGL(expand_bits_kernel, dim3((unsigned)std::min<int64_t>((n * dim * 8 + 255) / 256, (int64_t)res.num_cus * 64)),
+                         dim3(256), 0, res.stream, static_cast<const uint8_t*>(idx.data), n * dim, f.data());
+      knn_graph_bruteforce<float>(res, f.data(), n, dim * 8, K, M_L2Expanded, knn);
+      sync(res);
+    }
+    return;
+  }
+  if (p.build_algo == NN_DESCENT) {
+    cagra_set_norms(res, idx);  // cosine: the join needs |x|
+    knn_graph_nn_descent(res, idx.data, et, n, dim, K, metric, idx.norms.data(), (int)p.nn_descent_niter, knn);
+  } else if (small) {
+    if (et == elem_t::f32) {
+      knn_graph_bruteforce<float>(res, static_cast<const float*>(idx.data), n, dim, K, metric, knn);
+    } else if (et == elem_t::f16) {
+      knn_graph_bruteforce<__half>(res, static_cast<const __half*>(idx.data), n, dim, K, metric, knn);
+    } else {
+      dev_buf<float> f(res, (size_t)n * dim);
+      if (et == elem_t::i8)
+        hipLaunchKernelGGL((to_float_kernel<int8_t>), dim3(grid_blocks(n * dim, 256)), dim3(256), 0, res.stream,
+                           static_cast<const int8_t*>(idx.data), n * dim, f.data());
+      else
+        hipLaunchKernelGGL((to_float_kernel<uint8_t>), dim3(grid_blocks(n * dim, 256)), dim3(256), 0, res.stream,
+                           static_cast<const uint8_t*>(idx.data), n * dim, f.data());
+      knn_graph_bruteforce<float>(res, f.data(), n, dim, K, metric, knn);
+      sync(res);
+    }
+  } else {
+    knn_graph_ivf_pq(res, idx.data, et, n, dim, K, metric, knn);
+  }
+}
+
+// metric and dtype checks of a build (the reference's messages for BitwiseHamming: cagra_build.cuh:2220-2237)
+void cagra_check_build(const cuvsCagraIndexParams& p, elem_t et)
+{
+  const int metric = (int)p.metric;
+  CUVS_EXPECTS(metric_is_l2(metric) || metric == M_InnerProduct || metric == M_CosineExpanded || metric == M_BitwiseHamming,
+               "cagra: unsupported metric %d", metric);
+  if (metric != M_BitwiseHamming) return;
+  CUVS_EXPECTS(p.build_algo != IVF_PQ,
+               "IVF_PQ for CAGRA graph build does not support BitwiseHamming as a metric. Please use nn-descent or the iterative "
+               "CAGRA search build.");
+  CUVS_EXPECTS(et == elem_t::u8 || et == elem_t::i8,
+               "BitwiseHamming distance is only supported for int8_t and uint8_t data types. Current data type is not supported.");
+}
+
 std::unique_ptr<cagra_index> cagra_build(resources& res, const cuvsCagraIndexParams& p, const void* data, elem_t et,
                                          int64_t n, int64_t dim, bool is_host)
 {
   const int metric = (int)p.metric;
-  CUVS_EXPECTS(metric_is_l2(metric) || metric == M_InnerProduct || metric == M_CosineExpanded,
-               "cagra: unsupported metric %d", metric);
+  cagra_check_build(p, et);
   CUVS_EXPECTS(n > 1, "cagra: need at least two rows");
   auto idx    = std::make_unique<cagra_index>();
   idx->metric = metric;
@@ -1280,29 +1440,7 @@ std::unique_ptr<cagra_index> cagra_build(resources& res, const cuvsCagraIndexPar
   uint32_t K      = (uint32_t)std::min<int64_t>(std::max<size_t>(p.intermediate_graph_degree, degree), n - 1);
   idx->degree     = degree;
   dev_buf<uint32_t> knn(res, (size_t)n * K);
-  const bool small = n <= 200000 || p.build_algo == ITERATIVE_CAGRA_SEARCH;
-  if (p.build_algo == NN_DESCENT) {
-    cagra_set_norms(res, *idx);  // cosine: the join needs |x|
-    knn_graph_nn_descent(res, idx->data, et, n, dim, K, metric, idx->norms.data(), (int)p.nn_descent_niter, knn.data());
-  } else if (small) {
-    if (et == elem_t::f32) {
-      knn_graph_bruteforce<float>(res, static_cast<const float*>(idx->data), n, dim, K, metric, knn.data());
-    } else if (et == elem_t::f16) {
-      knn_graph_bruteforce<__half>(res, static_cast<const __half*>(idx->data), n, dim, K, metric, knn.data());
-    } else {
-      dev_buf<float> f(res, (size_t)n * dim);
-      if (et == elem_t::i8)
-        hipLaunchKernelGGL((to_float_kernel<int8_t>), dim3(grid_blocks(n * dim, 256)), dim3(256), 0, res.stream,
-                           static_cast<const int8_t*>(idx->data), n * dim, f.data());
-      else
-        hipLaunchKernelGGL((to_float_kernel<uint8_t>), dim3(grid_blocks(n * dim, 256)), dim3(256), 0, res.stream,
-                           static_cast<const uint8_t*>(idx->data), n * dim, f.data());
-      knn_graph_bruteforce<float>(res, f.data(), n, dim, K, metric, knn.data());
-      sync(res);
-    }
-  } else {
-    knn_graph_ivf_pq(res, idx->data, et, n, dim, K, metric, knn.data());
-  }
+  cagra_knn_graph(res, p, *idx, K, knn.data());
   idx->graph = dev_buf<uint32_t>::persistent((size_t)n * degree);
   optimize_graph(res, knn.data(), n, K, degree, idx->graph.data(), res.cagra_guarantee_connectivity);
   cagra_set_norms(res, *idx);
@@ -1624,7 +1762,8 @@ cuvsError_t cuvsCagraDeserialize(cuvsResources_t res_h, const char* filename, cu
       idx->dim    = (int64_t)r.scalar<uint32_t>();
       idx->degree = r.scalar<uint32_t>();
       idx->metric = r.scalar<int32_t>();
-      CUVS_EXPECTS(metric_is_l2(idx->metric) || idx->metric == M_InnerProduct || idx->metric == M_CosineExpanded,
+      CUVS_EXPECTS(metric_is_l2(idx->metric) || idx->metric == M_InnerProduct || idx->metric == M_CosineExpanded ||
+                     (idx->metric == M_BitwiseHamming && (idx->dtype == elem_t::u8 || idx->dtype == elem_t::i8)),
                    "cagra::deserialize: unsupported metric value %d", idx->metric);
       CUVS_EXPECTS(idx->degree > 0 && idx->degree <= 1024, "cagra::deserialize: graph_degree=%u exceeds maximum %u",
                    idx->degree, 1024u);
@@ -1665,6 +1804,8 @@ cuvsError_t cuvsCagraSerializeToHnswlib(cuvsResources_t res_h, const char* filen
     auto& res = *as_res(res_h);
     auto& idx = get_cagra(index);
     CUVS_EXPECTS(idx.data != nullptr && idx.n > 0, "Invalid CAGRA dataset of size 0 during serialization");
+    CUVS_EXPECTS(idx.metric != M_BitwiseHamming, "cagra::serialize_to_hnswlib: hnswlib has no BitwiseHamming space; a Hamming "
+                                                 "index cannot be exported");
     CUVS_EXPECTS(filename != nullptr, "filename is null");
     FILE* f = fopen(filename, "wb");
     CUVS_EXPECTS(f != nullptr, "Cannot open file %s", filename);
@@ -1883,5 +2024,40 @@ extern "C" __attribute__((visibility("default"))) int cuvsAmdCagraSearchPlan(cuv
     out[0] = pl.itopk; out[1] = pl.max_iterations; out[2] = pl.search_width; out[3] = (uint32_t)pl.ref_algo;
     out[4] = pl.ref_small_hash_bitlen; out[5] = pl.ref_hash_bitlen; out[6] = pl.ref_small_hash_reset_interval;
     out[7] = pl.ref_mc_num_cta_per_query; out[8] = pl.mc_max_iterations; out[9] = 0;
+  });
+}
+
+// Test hook (not part of the reference ABI): the intermediate kNN graph cuvsCagraBuild optimises, by params->build_algo and
+// params->metric, for a device or host dataset; knn_graph: uint32 [n, K] on the device (K <= n - 1).
+extern "C" __attribute__((visibility("default"))) cuvsError_t cuvsAmdCagraBuildKnnGraph(cuvsResources_t res_h,
+                                                                                        cuvsCagraIndexParams_t params,
+                                                                                        DLManagedTensor* dataset_tensor,
+                                                                                        DLManagedTensor* knn_tensor)
+{
+  return (cuvsError_t)translate_exceptions([=] {
+    using namespace cuvs_amd;
+    auto& res = *as_res(res_h);
+    CUVS_EXPECTS(params && dataset_tensor && knn_tensor, "null argument");
+    auto& ds = dataset_tensor->dl_tensor;
+    auto& kg = knn_tensor->dl_tensor;
+    CUVS_EXPECTS(ds.ndim == 2 && is_c_contiguous(ds), "dataset must be a row-major matrix");
+    CUVS_EXPECTS(dtype_is(kg.dtype, kDLUInt, 32) && kg.ndim == 2 && is_c_contiguous(kg) && is_device_accessible(kg) &&
+                   kg.shape[0] == ds.shape[0] && kg.shape[1] >= 1 && kg.shape[1] < ds.shape[0],
+                 "knn_graph must be a device uint32 [n, K] matrix with K < n");
+    cagra_index idx;
+    idx.metric = (int)params->metric;
+    idx.dtype  = elem_of(ds.dtype);
+    idx.n      = ds.shape[0];
+    idx.dim    = ds.shape[1];
+    cagra_check_build(*params, idx.dtype);
+    if (is_device_accessible(ds)) {
+      idx.data = dl_data(ds);
+    } else {
+      idx.owned = dev_buf<char>::persistent((size_t)idx.n * idx.dim * elem_size(idx.dtype));
+      copy_async(res, idx.owned.data(), dl_data(ds), idx.owned.bytes());
+      idx.data = idx.owned.data();
+    }
+    cagra_knn_graph(res, *params, idx, (uint32_t)kg.shape[1], static_cast<uint32_t*>(dl_data(kg)));
+    sync(res);
   });
 }

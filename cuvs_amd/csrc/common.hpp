@@ -320,7 +320,8 @@ void fill_dl_view(DLManagedTensor* out, void* data, DLDataType dt, int64_t rows,
 // distance metric ids (include/cuvs/distance/distance.h)
 enum metric_t : int {
   M_L2Expanded = 0, M_L2SqrtExpanded = 1, M_CosineExpanded = 2, M_L2Unexpanded = 4,
-  M_L2SqrtUnexpanded = 5, M_InnerProduct = 6
+  M_L2SqrtUnexpanded = 5, M_InnerProduct = 6,
+  M_BitwiseHamming = 20  // CAGRA and NN-descent over uint8 / int8 rows only (not in metric_supported, as in the reference)
 };
 inline bool metric_supported(int m)
 {

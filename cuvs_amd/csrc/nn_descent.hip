@@ -40,11 +40,45 @@ __device__ inline uint64_t xs64(uint64_t u)
   return u * 0x2545F4914F6CDD1DULL;
 }
 
+constexpr int kModeHamming = 3;  // BitwiseHamming over the bytes of uint8 / int8 rows
+
+// BitwiseHamming key of rows a, b: the same 8-lane teams and 16-byte pieces, XOR then popcount; the count is the distance
+__device__ inline uint32_t team_pair_hamming(const uint8_t* __restrict__ data, int64_t dim, uint32_t a, uint32_t b, int tl)
+{
+  const uint8_t* ra = data + (int64_t)a * dim;
+  const uint8_t* rb = data + (int64_t)b * dim;
+  uint32_t cnt      = 0u;
+  if (dim % 16 == 0 && (reinterpret_cast<uintptr_t>(data) & 15) == 0) {
+    for (int64_t d0 = (int64_t)tl * 16; d0 < dim; d0 += 128) {
+      const uint4 x = *reinterpret_cast<const uint4*>(ra + d0), y = *reinterpret_cast<const uint4*>(rb + d0);
+      cnt += (uint32_t)(__popc(x.x ^ y.x) + __popc(x.y ^ y.y) + __popc(x.z ^ y.z) + __popc(x.w ^ y.w));
+    }
+  } else {  // byte tail (dims that are not multiples of 16): a piece's 16 bytes loaded first (clamped index, no branch), then counted
+    for (int64_t d0 = (int64_t)tl * 16; d0 < dim; d0 += 128) {
+      uint32_t w[16];
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int64_t d = min(d0 + e, dim - 1);
+        w[e]            = (uint32_t)(ra[d] ^ rb[d]);
+      }
+#pragma unroll
+      for (int e = 0; e < 16; ++e) cnt += d0 + e < dim ? (uint32_t)__popc(w[e]) : 0u;
+    }
+  }
+  cnt += (uint32_t)__shfl_xor((int)cnt, 1, 64);
+  cnt += (uint32_t)__shfl_xor((int)cnt, 2, 64);
+  cnt += (uint32_t)__shfl_xor((int)cnt, 4, 64);
+  return float_to_key((float)cnt);
+}
+
 // distance key of rows a, b computed by an 8-lane team (lane tl of the team): smaller = closer
 template <typename T>
 __device__ inline uint32_t team_pair_key(const T* __restrict__ data, int64_t dim, uint32_t a, uint32_t b, int mode,
                                          const float* __restrict__ norms, int tl)
 {
+  if constexpr (sizeof(T) == 1) {
+    if (mode == kModeHamming) return team_pair_hamming(reinterpret_cast<const uint8_t*>(data), dim, a, b, tl);
+  }
   constexpr int VL = 16 / sizeof(T);
   const T* ra = data + (int64_t)a * dim;
   const T* rb = data + (int64_t)b * dim;
@@ -298,6 +332,19 @@ __global__ __launch_bounds__(kJoinThreads) void nnd_join_kernel(nnd_state st, co
 
 __global__ void nnd_inverse_perm_kernel(const uint32_t* __restrict__ perm, int64_t n, uint32_t* __restrict__ pos_of);
 
+// rows ids[i] (or r0 + i without ids) of bytes -> [cnt, 8 dim] floats of their bits (bit j of byte b -> column 8 b + j);
+// grid-stride
+__global__ void nnd_gather_bits_kernel(const uint8_t* __restrict__ data, int64_t dim, const uint32_t* __restrict__ ids, int64_t r0,
+                                       int64_t cnt, float* __restrict__ out)
+{
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < cnt * dim * 8; t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = t / (dim * 8), col = t - i * dim * 8;
+    const int64_t row = ids != nullptr ? (int64_t)ids[i] : r0 + i;
+    out[t] = (float)((data[row * dim + (col >> 3)] >> (col & 7)) & 1u);
+  }
+}
+inline dim3 nnd_bits_grid(int64_t elems, int num_cus) { return dim3((unsigned)std::min<int64_t>((elems + 255) / 256, (int64_t)num_cus * 64)); }
+
 template <typename T>
 void nnd_run(resources& res, const T* data, elem_t et, int64_t n, int64_t dim, uint32_t K_out, int mode, const float* norms,
              int n_iters, uint32_t* knn_out, uint32_t* keys_out, float termination_threshold)
@@ -333,33 +380,49 @@ void nnd_run(resources& res, const T* data, elem_t et, int64_t n, int64_t dim, u
   const unsigned g4 = grid_blocks(n, 4);
   // ---- coarse clustering for the initial lists: clusters of ~4 K rows (balanced k-means on a strided sample)
   dev_buf<uint32_t> perm, pos_of, cl_off, labels;
-  const int64_t n_clusters = std::min<int64_t>(65536, n / (4 * (int64_t)K));
+  int64_t n_clusters = std::min<int64_t>(65536, n / (4 * (int64_t)K));
+  // BitwiseHamming: the k-means runs on the rows expanded to 0/1 floats (8 dim columns), where squared L2 IS the Hamming
+  // distance - k-means over the byte values would group rows by a distance the graph does not use
+  const bool ham     = mode == kModeHamming;
+  const int64_t kdim = ham ? 8 * dim : dim;
   if (n_clusters >= 2) {
-    const int64_t n_train = std::min<int64_t>(n, std::max<int64_t>(n_clusters * 64, 100000));
+    int64_t n_train = std::min<int64_t>(n, std::max<int64_t>(n_clusters * 64, 100000));
+    if (ham) {  // the expansion is 32x the rows' bytes: the sample is capped at 2^30 floats (4 GB), the cluster count follows it
+      n_train    = std::min<int64_t>(n_train, std::max<int64_t>(64, (int64_t(1) << 30) / kdim));
+      n_clusters = std::max<int64_t>(2, std::min<int64_t>(n_clusters, n_train / 32));
+    }
     const int64_t stride  = std::max<int64_t>(1, n / n_train);
     const int64_t nt      = n / stride;
-    dev_buf<float> train(res, (size_t)nt * dim), centers(res, (size_t)n_clusters * dim);
+    dev_buf<float> train(res, (size_t)nt * kdim), centers(res, (size_t)n_clusters * kdim);
     {
       std::vector<uint32_t> h_ids(nt);
       for (int64_t i = 0; i < nt; ++i) h_ids[i] = (uint32_t)(i * stride);
       dev_buf<uint32_t> d_ids(res, nt);
       copy_async(res, d_ids.data(), h_ids.data(), nt * sizeof(uint32_t));
-      load_gather_as_float(res, data, et, false, dim, d_ids.data(), nt, train.data());
+      if (ham)
+        hipLaunchKernelGGL(nnd_gather_bits_kernel, nnd_bits_grid(nt * kdim, res.num_cus), dim3(256), 0, res.stream,
+                           reinterpret_cast<const uint8_t*>(data), dim, d_ids.data(), (int64_t)0, nt, train.data());
+      else
+        load_gather_as_float(res, data, et, false, dim, d_ids.data(), nt, train.data());
       sync(res);
     }
     if (mode == 2) normalize_rows(res, train.data(), nt, dim);
     kmeans_params kp;
     kp.n_iters = 10;
-    kmeans_balanced_fit(res, train.data(), nt, dim, (int)n_clusters, kp, centers.data());
+    kmeans_balanced_fit(res, train.data(), nt, kdim, (int)n_clusters, kp, centers.data());
     train.release();
     labels = dev_buf<uint32_t>(res, n);
-    const int64_t batch = std::max<int64_t>(1024, std::min<int64_t>(n, (int64_t(1) << 28) / dim));
-    dev_buf<float> xb(res, (size_t)std::min(batch, n) * dim);
+    const int64_t batch = std::max<int64_t>(1024, std::min<int64_t>(n, (int64_t(1) << 28) / kdim));
+    dev_buf<float> xb(res, (size_t)std::min(batch, n) * kdim);
     for (int64_t r0 = 0; r0 < n; r0 += batch) {
       const int64_t cnt = std::min(batch, n - r0);
-      load_range_as_float(res, data, et, false, dim, r0, cnt, xb.data());
+      if (ham)
+        hipLaunchKernelGGL(nnd_gather_bits_kernel, nnd_bits_grid(cnt * kdim, res.num_cus), dim3(256), 0, res.stream,
+                           reinterpret_cast<const uint8_t*>(data), dim, (const uint32_t*)nullptr, r0, cnt, xb.data());
+      else
+        load_range_as_float(res, data, et, false, dim, r0, cnt, xb.data());
       if (mode == 2) normalize_rows(res, xb.data(), cnt, dim);
-      kmeans_predict<float>(res, xb.data(), cnt, dim, centers.data(), (int)n_clusters, labels.data() + r0);
+      kmeans_predict<float>(res, xb.data(), cnt, kdim, centers.data(), (int)n_clusters, labels.data() + r0);
     }
     perm   = dev_buf<uint32_t>(res, n);
     pos_of = dev_buf<uint32_t>(res, n);
@@ -426,7 +489,11 @@ void knn_graph_nn_descent(resources& res, const void* data, elem_t et, int64_t n
                           const float* norms, int n_iters, uint32_t* knn, uint32_t* keys_out, float termination_threshold)
 {
   CUVS_EXPECTS(n > (int64_t)K, "nn_descent: need more rows than the graph degree");
-  const int mode = metric == M_InnerProduct ? 1 : (metric == M_CosineExpanded ? 2 : 0);
+  // detail/nn_descent.cuh:1495-1498
+  CUVS_EXPECTS(metric != M_BitwiseHamming || et == elem_t::u8 || et == elem_t::i8,
+               "Data type needs to be int8 or uint8 for NN Descent to run with BitwiseHamming distance.");
+  const int mode = metric == M_BitwiseHamming ? kModeHamming
+                                              : (metric == M_InnerProduct ? 1 : (metric == M_CosineExpanded ? 2 : 0));
   CUVS_EXPECTS(mode != 2 || norms != nullptr, "nn_descent: cosine needs row norms");
   if (n_iters <= 0) n_iters = 20;
   switch (et) {
@@ -529,7 +596,7 @@ cuvsError_t cuvsNNDescentBuild(cuvsResources_t res_h, cuvsNNDescentIndexParams_t
     const elem_t et = elem_of(ds.dtype);  // fails for unsupported dtypes
     const int64_t n = ds.shape[0], dim = ds.shape[1];
     const int metric = (int)params->metric;
-    CUVS_EXPECTS(metric_is_l2(metric) || metric == M_InnerProduct || metric == M_CosineExpanded,
+    CUVS_EXPECTS(metric_is_l2(metric) || metric == M_InnerProduct || metric == M_CosineExpanded || metric == M_BitwiseHamming,
                  "nn_descent: unsupported metric %d", metric);
     const uint32_t degree = (uint32_t)params->graph_degree;
     uint32_t K = (uint32_t)std::max(params->intermediate_graph_degree, params->graph_degree);

@@ -66,6 +66,13 @@ class IndexParams:
         self._algo = _BUILD_ALGOS[build_algo]
         self.metric = metric
 
+    def _c_build_algo(self):
+        # "auto" builds with IVF-PQ as in the reference's Python layer (cagra.pyx), except for bitwise_hamming, which IVF-PQ
+        # does not support: there the library's AUTO rule applies (exact graph up to 200000 rows, NN-descent above)
+        if self._algo == 0 and self.metric == "bitwise_hamming":
+            return 0
+        return max(self._algo, 1) if self._algo != 3 else 3
+
     def __del__(self):
         try:
             lib().cuvsCagraIndexParamsDestroy(self._p)
@@ -137,7 +144,7 @@ def build(index_params, dataset, resources=None):
     ds = dataset.contiguous() if isinstance(dataset, torch.Tensor) else np.ascontiguousarray(dataset)
     idx = Index()
     t = Tensor(ds)
-    index_params._p.contents.build_algo = max(index_params._algo, 1) if index_params._algo != 3 else 3
+    index_params._p.contents.build_algo = index_params._c_build_algo()
     check(lib().cuvsAmdCagraSetGuaranteeConnectivity(resources.get_c_obj(), C.c_int(int(index_params.guarantee_connectivity))))
     try:
         check(lib().cuvsCagraBuild(resources.get_c_obj(), index_params._p, t.ptr, idx._p))
@@ -181,6 +188,22 @@ def optimize(knn_graph, graph_degree, guarantee_connectivity=False, resources=No
     tk.m.dl_tensor.dtype.code = 1  # uint32
     to.m.dl_tensor.dtype.code = 1
     check(lib().cuvsAmdCagraOptimize(resources.get_c_obj(), tk.ptr, to.ptr, C.c_int(int(guarantee_connectivity))))
+    return out
+
+
+@auto_sync_resources
+def build_knn_graph(index_params, dataset, k, resources=None):
+    """cuvsAmdCagraBuildKnnGraph: the intermediate kNN graph [n, k] (uint32 in an int32 tensor, on the device) that build()
+    optimises, made by index_params' build algorithm and metric; self matches excluded."""
+    ds = dataset.contiguous() if isinstance(dataset, torch.Tensor) else np.ascontiguousarray(dataset)
+    out = torch.empty((ds.shape[0], k), dtype=torch.int32, device="cuda")
+    t, to = Tensor(ds), Tensor(out)
+    to.m.dl_tensor.dtype.code = 1  # uint32
+    index_params._p.contents.build_algo = index_params._c_build_algo()
+    try:
+        check(lib().cuvsAmdCagraBuildKnnGraph(resources.get_c_obj(), index_params._p, t.ptr, to.ptr))
+    finally:
+        index_params._p.contents.build_algo = 1
     return out
 
 
@@ -240,7 +263,7 @@ def merge(index_params, indices, resources=None, filter=None):
     flt, keep = make_filter(filter)
     fn = lib().cuvsCagraMerge
     fn.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, cuvsFilter, C.c_void_p]
-    index_params._p.contents.build_algo = max(index_params._algo, 1) if index_params._algo != 3 else 3
+    index_params._p.contents.build_algo = index_params._c_build_algo()
     check(fn(resources.get_c_obj(), index_params._p, arr, C.c_size_t(len(indices)), flt, out._p))
     del keep
     index_params._p.contents.build_algo = 1

@@ -13,6 +13,7 @@
 #include <cuvs/neighbors/cagra.h>
 #include <cuvs/neighbors/nn_descent.h>
 #include <cuvs/neighbors/refine.h>
+#include <cuvs/preprocessing/quantize/binary.h>
 #ifdef CUVS_BUILD_MG_ALGOS
 #include <cuvs/neighbors/mg_common.h>
 #include <cuvs/neighbors/mg_ivf_flat.h>

@@ -4,8 +4,10 @@
 #pragma once
 #include <cuvs/core/c_api.h>
 #include <cuvs/core/export.h>
+#include <cuvs/neighbors/cagra.h>
 #include <cuvs/neighbors/common.h>
 #include <cuvs/neighbors/ivf_pq.h>
+#include <cuvs/preprocessing/quantize/binary.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -41,9 +43,21 @@ CUVS_EXPORT cuvsError_t cuvsAmdCagraSetGuaranteeConnectivity(cuvsResources_t res
 CUVS_EXPORT cuvsError_t cuvsAmdCagraOptimize(cuvsResources_t res, DLManagedTensor* knn_graph, DLManagedTensor* graph,
                                              int guarantee_connectivity);
 
+/* The intermediate kNN graph that cuvsCagraBuild optimises, made by params->build_algo for params->metric: uint32 [n, K] on
+ * the device, K < n. Exposes the graph step alone (for BitwiseHamming: NN-descent, or the exact graph of
+ * ITERATIVE_CAGRA_SEARCH / AUTO up to 200000 rows). */
+CUVS_EXPORT cuvsError_t cuvsAmdCagraBuildKnnGraph(cuvsResources_t res, cuvsCagraIndexParams_t params, DLManagedTensor* dataset,
+                                                  DLManagedTensor* knn_graph);
+
 /* index.codes_layout() of the reference's C++ index (cpp/include/cuvs/neighbors/ivf_pq.hpp:40-90; the C ABI sets the layout in
  * cuvsIvfPqIndexParams but has no getter): 0 = CUVS_IVF_PQ_LIST_LAYOUT_FLAT, 1 = CUVS_IVF_PQ_LIST_LAYOUT_INTERLEAVED. */
 CUVS_EXPORT cuvsError_t cuvsAmdIvfPqIndexGetCodesLayout(cuvsIvfPqIndex_t index, int* layout);
+
+/* The trained thresholds of a binary quantizer (cuvs::preprocessing::quantize::binary::quantizer<T>::threshold; the C ABI
+ * has no getter): copied into `out`, a 1-D tensor of the quantizer's dtype and length dim on the host or the device. A ZERO
+ * quantizer holds no thresholds: out must then have length 0. */
+CUVS_EXPORT cuvsError_t cuvsAmdBinaryQuantizerGetThreshold(cuvsResources_t res, cuvsBinaryQuantizer_t quantizer,
+                                                           DLManagedTensor* out);
 
 /* Measurement helpers of bench.py (no reference counterpart). cuvsAmdProfileEnable / cuvsAmdProfileCollect: HIP events
  * around the named kernels on the handle's stream (Collect sums and resets the records of `name`, returns the launch count).
