@@ -201,6 +201,7 @@ tuning load_tuning_from_env()
   t.pq_wide          = geti("CUVS_AMD_PQ_WIDE", 1);
   t.pq_wide_heads    = geti("CUVS_AMD_PQ_WIDE_HEADS", 0);
   t.pq_wide_blocks   = geti("CUVS_AMD_PQ_WIDE_BLOCKS", 1);
+  if (const char* e = getenv("CUVS_AMD_PQ_ENCODE")) t.pq_encode_plain = strcmp(e, "plain") == 0;
   t.pq3_surv_cap     = geti("CUVS_AMD_PQ3_SURV_CAP", 0);
   t.pq_qcap          = geti("CUVS_AMD_PQ_QCAP", 0);
   t.scan_debug       = geti("CUVS_AMD_SCAN_DEBUG", 0);

@@ -14,6 +14,8 @@
 #include <cuvs/neighbors/nn_descent.h>
 #include <cuvs/neighbors/refine.h>
 #include <cuvs/preprocessing/quantize/binary.h>
+#include <cuvs/preprocessing/quantize/pq.h>
+#include <cuvs/preprocessing/quantize/scalar.h>
 #ifdef CUVS_BUILD_MG_ALGOS
 #include <cuvs/neighbors/mg_common.h>
 #include <cuvs/neighbors/mg_ivf_flat.h>

@@ -8,6 +8,7 @@
 #include <cuvs/neighbors/common.h>
 #include <cuvs/neighbors/ivf_pq.h>
 #include <cuvs/preprocessing/quantize/binary.h>
+#include <cuvs/preprocessing/quantize/pq.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -58,6 +59,18 @@ CUVS_EXPORT cuvsError_t cuvsAmdIvfPqIndexGetCodesLayout(cuvsIvfPqIndex_t index, 
  * quantizer holds no thresholds: out must then have length 0. */
 CUVS_EXPORT cuvsError_t cuvsAmdBinaryQuantizerGetThreshold(cuvsResources_t res, cuvsBinaryQuantizer_t quantizer,
                                                            DLManagedTensor* out);
+
+/* A product quantizer over caller-supplied codebooks (no reference counterpart; books trained elsewhere, and the tests' way
+ * to pin the encoder without k-means). pq_codebook: device fp32 [pq_dim * 2^pq_bits, pq_len] when params->use_subspaces,
+ * else [2^pq_bits, pq_len]; params->pq_dim must be set. vq_codebook: device fp32 [vq_n_centers, pq_dim * pq_len] or NULL
+ * (then use_vq is off whatever params says). The books are copied. */
+CUVS_EXPORT cuvsError_t cuvsAmdProductQuantizerFromCodebooks(cuvsResources_t res, cuvsProductQuantizerParams_t params,
+                                                             DLManagedTensor* pq_codebook, DLManagedTensor* vq_codebook,
+                                                             cuvsProductQuantizer_t quantizer);
+/* Encoder launches since the library was loaded (the tests' proof of which path ran): out = {default encoder, plain encoder,
+ * default encoder with more than one row per lane (taken when ceil(n / (256 R)) >= 2 * compute units; R = 4 up to pq_len 8,
+ * 2 up to pq_len 32)}; out[2] is part of out[0]. */
+CUVS_EXPORT void cuvsAmdPqEncodeCounters(unsigned long long out[3]);
 
 /* Measurement helpers of bench.py (no reference counterpart). cuvsAmdProfileEnable / cuvsAmdProfileCollect: HIP events
  * around the named kernels on the handle's stream (Collect sums and resets the records of `name`, returns the launch count).
