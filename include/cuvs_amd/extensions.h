@@ -4,6 +4,7 @@
 #pragma once
 #include <cuvs/core/c_api.h>
 #include <cuvs/core/export.h>
+#include <cuvs/neighbors/all_neighbors.h>
 #include <cuvs/neighbors/cagra.h>
 #include <cuvs/neighbors/common.h>
 #include <cuvs/neighbors/ivf_pq.h>
@@ -71,6 +72,21 @@ CUVS_EXPORT cuvsError_t cuvsAmdProductQuantizerFromCodebooks(cuvsResources_t res
  * default encoder with more than one row per lane (taken when ceil(n / (256 R)) >= 2 * compute units; R = 4 up to pq_len 8,
  * 2 up to pq_len 32)}; out[2] is part of out[0]. */
 CUVS_EXPORT void cuvsAmdPqEncodeCounters(unsigned long long out[3]);
+
+/* The two steps of a batched cuvsAllNeighborsBuild on their own (no reference counterpart; how the tests pin the batched
+ * build to a restatement). cuvsAmdAllNeighborsPartition: the clustering step, same code path as the build and deterministic -
+ * dataset_host fp32 [n, dim] on the host; centroids_out fp32 [n_clusters, dim] (host or device); nearest_clusters_out int64
+ * [n, overlap_factor] on the host, row i = the clusters row i is assigned to, nearest first. */
+CUVS_EXPORT cuvsError_t cuvsAmdAllNeighborsPartition(cuvsResources_t res, cuvsAllNeighborsIndexParams_t params,
+                                                     DLManagedTensor* dataset_host, DLManagedTensor* centroids_out,
+                                                     DLManagedTensor* nearest_clusters_out);
+/* cuvsAmdAllNeighborsMerge: one launch of the remap-merge kernel. All tensors on the device: inverted_indices int64 [m] (the
+ * cluster's global row ids), batch_indices int64 [m, k] LOCAL ids, batch_distances fp32 [m, k]; global_indices int64 [n, k]
+ * and global_distances fp32 [n, k] are updated in place. select_min 0: larger distances are better (inner product). */
+CUVS_EXPORT cuvsError_t cuvsAmdAllNeighborsMerge(cuvsResources_t res, DLManagedTensor* inverted_indices,
+                                                 DLManagedTensor* batch_indices, DLManagedTensor* batch_distances,
+                                                 DLManagedTensor* global_indices, DLManagedTensor* global_distances,
+                                                 int select_min);
 
 /* Measurement helpers of bench.py (no reference counterpart). cuvsAmdProfileEnable / cuvsAmdProfileCollect: HIP events
  * around the named kernels on the handle's stream (Collect sums and resets the records of `name`, returns the launch count).
