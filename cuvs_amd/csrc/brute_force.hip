@@ -393,6 +393,26 @@ __global__ void transpose_copy_kernel(const char* src, char* dst, int64_t rows, 
 }
 
 }  // namespace
+
+// tiered_index.hip: the tail rows of a tiered index and their stored norms, searched in place
+void bf_search_view(resources& res, int metric, const float* data, int64_t n, int64_t dim, const float* norms,
+                    const float* queries, int64_t m, int k, int64_t* neighbors, float* distances, const uint32_t* bits)
+{
+  bf_index idx;
+  idx.metric = metric;
+  idx.n      = n;
+  idx.dim    = dim;
+  idx.ld     = dim;
+  idx.data   = data;
+  struct borrowed {  // the norms stay the caller's
+    dev_buf<float>& b;
+    ~borrowed() { b.ptr = nullptr; b.n = 0; }
+  } guard{idx.norms};
+  idx.norms.ptr = const_cast<float*>(norms);
+  idx.norms.n   = norms != nullptr ? (size_t)n : 0;
+  bf_search_typed<float>(res, idx, queries, m, dim, k, neighbors, distances, bits, bits != nullptr ? (int)BITSET : (int)NO_FILTER);
+}
+
 }  // namespace cuvs_amd
 
 using namespace cuvs_amd;

@@ -1457,6 +1457,15 @@ void cagra_index_info(uintptr_t addr, int64_t* size, int* metric)
   *metric   = idx->metric;
 }
 
+// tiered_index.hip: the rows a viewing index was built over have moved (same bytes, new address)
+void cagra_repoint_dataset(uintptr_t addr, const void* data)
+{
+  CUVS_EXPECTS(addr != 0, "cagra index is empty");
+  auto* idx = reinterpret_cast<cagra_index*>(addr);
+  CUVS_EXPECTS(idx->owned.data() == nullptr, "cagra index owns its rows: nothing to re-point");
+  idx->data = data;
+}
+
 }  // namespace cuvs_amd
 
 using namespace cuvs_amd;

@@ -107,6 +107,7 @@ struct tuning {
   int flat_head_probes  = -1;     // CUVS_AMD_FLAT_HEAD_PROBES
   int cagra_pq_lists = 0, cagra_pq_probes = 0, cagra_kpq = 0, cagra_rank_chunk = 0, prune_dbg = 0;  // CUVS_AMD_CAGRA_*, CUVS_AMD_PRUNE_DBG
   bool cagra_auto_multi = false;  // CUVS_AMD_CAGRA_AUTO=multi
+  int tiered_path       = 0;      // CUVS_AMD_TIERED_PATH=composed | fused: the tail phase of a tiered search always through the composed path (threshold append + merge kernel; comparator) or, where its shapes allow, the single-launch kernel
   bool native_format    = false;  // CUVS_AMD_NATIVE_FORMAT=1: *Serialize writes this library's own container
 };
 tuning load_tuning_from_env();

@@ -220,6 +220,7 @@ tuning load_tuning_from_env()
   t.cagra_rank_chunk   = geti("CUVS_AMD_CAGRA_RANK_CHUNK", 0);
   t.prune_dbg          = geti("CUVS_AMD_PRUNE_DBG", 0);
   if (const char* e = getenv("CUVS_AMD_CAGRA_AUTO")) t.cagra_auto_multi = e[0] == 'm';
+  if (const char* e = getenv("CUVS_AMD_TIERED_PATH")) t.tiered_path = strcmp(e, "composed") == 0 ? 1 : (strcmp(e, "fused") == 0 ? 2 : 0);
   if (const char* e = getenv("CUVS_AMD_NATIVE_FORMAT")) t.native_format = e[0] == '1';
   return t;
 }

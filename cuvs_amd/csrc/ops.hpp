@@ -136,8 +136,17 @@ int64_t cagra_mst_optimize(resources& res, const uint32_t* knn, int64_t n, uint3
 void refine(resources& res, const void* data, elem_t et, int64_t n, int64_t dim, const void* queries, int64_t m,
             const int64_t* cand, int n_cand, int k, int metric, int64_t* out_i, float* out_d);
 
+// ---------------------------------------------------------------- brute_force.hip
+// cuvsBruteForceSearch over fp32 rows that somebody else holds: data [n, dim] with its canonical norms (|x|^2, cosine |x|;
+// nullptr for inner product), both on the device. bits: optional bitset over the n rows (1 keeps). Results as
+// cuvsBruteForceSearch: missing slots hold the worst value and id -1, filtered rows the worst value.
+void bf_search_view(resources& res, int metric, const float* data, int64_t n, int64_t dim, const float* norms,
+                    const float* queries, int64_t m, int k, int64_t* neighbors, float* distances, const uint32_t* bits);
+
 // ---------------------------------------------------------------- mg.hip helpers (defined next to the index structs)
 void ivf_flat_index_info(uintptr_t addr, int64_t* size, int* metric);
 void cagra_index_info(uintptr_t addr, int64_t* size, int* metric);
+// a CAGRA index that views its rows (built from a device dataset) follows them to a new address holding the same bytes
+void cagra_repoint_dataset(uintptr_t addr, const void* data);
 
 }  // namespace cuvs_amd

@@ -8,6 +8,7 @@
 #include <cuvs/neighbors/cagra.h>
 #include <cuvs/neighbors/common.h>
 #include <cuvs/neighbors/ivf_pq.h>
+#include <cuvs/neighbors/tiered_index.h>
 #include <cuvs/preprocessing/quantize/binary.h>
 #include <cuvs/preprocessing/quantize/pq.h>
 #include <stdint.h>
@@ -87,6 +88,40 @@ CUVS_EXPORT cuvsError_t cuvsAmdAllNeighborsMerge(cuvsResources_t res, DLManagedT
                                                  DLManagedTensor* batch_indices, DLManagedTensor* batch_distances,
                                                  DLManagedTensor* global_indices, DLManagedTensor* global_distances,
                                                  int select_min);
+
+/* Tiered index (cuvsTieredIndex*). cuvsAmdTieredIndexGetInfo: rows held, rows served by the ANN tier (0: no
+ * ANN tier), rows the storage has room for, row width; any out pointer may be NULL. cuvsAmdTieredIndexCompact: the reference's
+ * C++ tiered_index::compact (its C ABI has none) - rebuilds the ANN tier over all rows with the stored build parameters when
+ * the tail is not empty. */
+CUVS_EXPORT cuvsError_t cuvsAmdTieredIndexGetInfo(cuvsTieredIndex_t index, int64_t* size, int64_t* ann_rows, int64_t* capacity,
+                                                  int64_t* dim);
+CUVS_EXPORT cuvsError_t cuvsAmdTieredIndexCompact(cuvsResources_t res, cuvsTieredIndex_t index);
+/* The two inputs of a tiered search's merge for the same call (arguments as cuvsTieredIndexSearch; all four outputs [m, k] on the
+ * device, int64 / fp32): ann_* = what the ANN tier's own search returns, with that tier's own padding for missing slots; tail_* =
+ * the exact top-k of the tail rows with global ids, INT64_MAX / FLT_MAX (-FLT_MAX for inner product) in the slots the tail cannot
+ * fill. An absent tier's outputs are all padding (INT64_MAX and the worst distance). */
+CUVS_EXPORT cuvsError_t cuvsAmdTieredIndexSearchTiers(cuvsResources_t res, void* search_params, cuvsTieredIndex_t index,
+                                                      DLManagedTensor* queries, DLManagedTensor* ann_neighbors,
+                                                      DLManagedTensor* ann_distances, DLManagedTensor* tail_neighbors,
+                                                      DLManagedTensor* tail_distances, cuvsFilter prefilter);
+/* The tail phase of a tiered search on its own (how the tests pin the kernels to a restatement): seed_neighbors int64 / seed_distances
+ * fp32 [m, k] play the ANN result over rows [0, ann_rows) (padding recognised by id), tail fp32 [n_tail, dim] holds the rows with
+ * global ids ann_rows + j, bitset (NULL or uint32 words over the global ids, 1 keeps) filters the tail; neighbors / distances [m, k]
+ * receive the merged result. All tensors on the device. path 0: the library's choice, 1: the composed path (threshold append + merge
+ * kernel), 2: the single-launch small-batch kernel (refused beyond its shapes). */
+CUVS_EXPORT cuvsError_t cuvsAmdTieredTailSearch(cuvsResources_t res, cuvsDistanceType metric, DLManagedTensor* tail, int64_t ann_rows,
+                                                DLManagedTensor* queries, DLManagedTensor* seed_neighbors,
+                                                DLManagedTensor* seed_distances, DLManagedTensor* bitset, int path,
+                                                DLManagedTensor* neighbors, DLManagedTensor* distances);
+/* One launch of the tiered merge kernel: A int64 / fp32 [m, k] (an ANN result over rows [0, ann_rows), padding recognised by id) and
+ * B int64 / fp32 [m, kb] (entries with id INT64_MAX are padding) -> the first k of the union by (distance, id), inner product by
+ * (-distance, id), into out_* [m, k]; the slots that remain hold INT64_MAX / the worst distance. All tensors on the device. */
+CUVS_EXPORT cuvsError_t cuvsAmdTieredMerge(cuvsResources_t res, DLManagedTensor* a_neighbors, DLManagedTensor* a_distances,
+                                           DLManagedTensor* b_neighbors, DLManagedTensor* b_distances, int64_t ann_rows,
+                                           int select_min, DLManagedTensor* out_neighbors, DLManagedTensor* out_distances);
+/* Launch counts since the library was loaded (the tests' proof of which path ran): out = {composed tail phases, single-launch tail
+ * phases, single-launch tail phases redone because an append buffer overflowed}. */
+CUVS_EXPORT void cuvsAmdTieredCounters(unsigned long long out[3]);
 
 /* Measurement helpers of bench.py (no reference counterpart). cuvsAmdProfileEnable / cuvsAmdProfileCollect: HIP events
  * around the named kernels on the handle's stream (Collect sums and resets the records of `name`, returns the launch count).
