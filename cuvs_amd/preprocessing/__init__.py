@@ -1,2 +1,3 @@
 """Preprocessing (reference: python/cuvs/cuvs/preprocessing)."""
+from . import pca  # noqa: F401
 from . import quantize  # noqa: F401

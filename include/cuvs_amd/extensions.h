@@ -136,6 +136,10 @@ CUVS_EXPORT void cuvsAmdIvfPqLastFilterStats(unsigned long long out[4]);
  * shared overflow list */
 CUVS_EXPORT void cuvsAmdIvfPqLastFilterStats6(unsigned long long out[6]);
 
+/* Sweeps of the Jacobi eigensolver that the calling thread's last cuvsPcaFit / cuvsPcaFitTransform ran (a sweep that rotated
+ * nothing is not counted). Test and tuning hook for cuvsPcaParams::tol and n_iterations. */
+CUVS_EXPORT cuvsError_t cuvsAmdPcaLastSweeps(int* sweeps);
+
 #ifdef __cplusplus
 }
 #endif
