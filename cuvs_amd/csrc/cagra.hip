@@ -41,6 +41,7 @@ struct cagra_index {
   // optional: the source id of every row (cagra.hpp index::source_indices, written by the reference's serializer as content-map
   // bit 1, cagra_serialize.cuh:72-83): a search reports source_indices[row] instead of the row (search_multi_cta.cuh:266-272)
   dev_buf<uint32_t> source_indices;
+  int64_t source_bits = 0;  // max(source_indices) + 1, found once at load: the bits a filter over source ids has to hold
 };
 
 // canonical row norms of the dataset for the cosine metric (no-op otherwise)
@@ -428,7 +429,8 @@ struct search_args {
   const void* data;
   const uint32_t* graph;
   const void* queries;
-  const uint32_t* filter_bits;  // optional bitset (1 keeps)
+  const uint32_t* filter_bits;  // optional bitset over source ids (1 keeps)
+  const uint32_t* source;       // optional source id of every row (index::source_indices); nullptr: a row is its own source id
   void* out_idx;                // uint32 or int64 [nq, k]
   float* out_dist;
   int64_t n, dim;
@@ -442,6 +444,13 @@ struct search_args {
   // per wave and counter at the end of the walk; nullptr: not counted.
   unsigned long long* work = nullptr;
 };
+
+// the filter is evaluated on the source id of a row (to_source_index, search_single_cta_jit.cuh:86-87,306-309)
+__device__ inline bool filter_keeps(const search_args& a, uint32_t node)
+{
+  const uint32_t sid = a.source != nullptr ? a.source[node] : node;
+  return (a.filter_bits[sid >> 5] >> (sid & 31)) & 1u;
+}
 
 __device__ inline uint32_t hash_slot(uint32_t key, uint32_t bits) { return (key ^ (key >> bits)) & ((1u << bits) - 1u); }
 
@@ -739,7 +748,7 @@ __global__ __launch_bounds__(64) void cagra_search_kernel(search_args a)
     const uint32_t i = base + lane;
     bool ok          = i < a.itopk && idx[i] != kInvalidNode;
     uint32_t node    = ok ? (idx[i] & ~kParentFlag) : 0;
-    if (ok && a.filter_bits) ok = (a.filter_bits[node >> 5] >> (node & 31)) & 1u;
+    if (ok && a.filter_bits) ok = filter_keeps(a, node);
     const unsigned long long m = __ballot(ok);
     const uint32_t rank        = written + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
     if (ok && rank < a.k) {
@@ -962,7 +971,7 @@ __global__ __launch_bounds__(1024) void cagra_search_multi_kernel(mw_args m)
       if (!(e & kParentFlag)) {
         drop = trav_contains(trav, m.trav_bits, e);
       } else if (a.filter_bits != nullptr && (e & ~kParentFlag) == parent) {
-        drop = !((a.filter_bits[parent >> 5] >> (parent & 31)) & 1u);
+        drop = !filter_keeps(a, parent);
       }
       if (drop) { idx[i] = kInvalidNode; keys[i] = 0xffffffffu; }
     }
@@ -983,7 +992,7 @@ __global__ __launch_bounds__(1024) void cagra_search_multi_kernel(mw_args m)
     uint32_t kk = lane < (int)kMwTopk ? keys[lane] : 0xffffffffu;
     bool ok = e != kInvalidNode;
     const uint32_t node = e & ~kParentFlag;
-    if (ok && a.filter_bits) ok = (a.filter_bits[node >> 5] >> (node & 31)) & 1u;
+    if (ok && a.filter_bits) ok = filter_keeps(a, node);
     if (ok && !(e & kParentFlag)) ok = trav_insert(trav, m.trav_bits, node);
     if (lane < (int)kMwTopk) {
       mkeys[wave * kMwTopk + lane] = ok ? kk : 0xffffffffu;
@@ -1046,6 +1055,30 @@ int64_t count_set_bits(resources& res, const uint32_t* bits, int64_t n_bits)
   dev_buf<unsigned long long> cnt(res, 1);
   HIP_TRY(hipMemsetAsync(cnt.data(), 0, sizeof(unsigned long long), res.stream));
   hipLaunchKernelGGL(popcount_kernel, dim3(256), dim3(256), 0, res.stream, bits, n_bits, cnt.data());
+  unsigned long long h = 0;
+  HIP_TRY(hipMemcpyAsync(&h, cnt.data(), sizeof(h), hipMemcpyDeviceToHost, res.stream));
+  HIP_TRY(hipStreamSynchronize(res.stream));
+  return (int64_t)h;
+}
+
+// rows whose source id has its bit set (an index with source_indices: the filter is a bitset over source ids)
+__global__ void count_kept_rows_kernel(const uint32_t* __restrict__ bits, const uint32_t* __restrict__ source, int64_t n,
+                                       unsigned long long* __restrict__ out)
+{
+  unsigned long long c = 0;
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
+    const uint32_t sid = source[r];
+    c += (bits[sid >> 5] >> (sid & 31)) & 1u;
+  }
+  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(out, c);
+}
+
+int64_t count_kept_rows(resources& res, const uint32_t* bits, const uint32_t* source, int64_t n)
+{
+  dev_buf<unsigned long long> cnt(res, 1);
+  HIP_TRY(hipMemsetAsync(cnt.data(), 0, sizeof(unsigned long long), res.stream));
+  hipLaunchKernelGGL(count_kept_rows_kernel, dim3(256), dim3(256), 0, res.stream, bits, source, n, cnt.data());
   unsigned long long h = 0;
   HIP_TRY(hipMemcpyAsync(&h, cnt.data(), sizeof(h), hipMemcpyDeviceToHost, res.stream));
   HIP_TRY(hipStreamSynchronize(res.stream));
@@ -1147,7 +1180,7 @@ cagra_plan make_cagra_plan(const cuvsCagraSearchParams& p, int64_t n_rows, uint3
 }
 
 // rows -> source ids of an index that carries them (search_multi_cta.cuh:266-272, search_multi_kernel.cuh:658-668); slots without a
-// neighbour stay as they are
+// neighbour stay as they are. n: entries of `source` itself
 __global__ void cagra_source_ids_kernel(void* out_idx, int64_t n_out, int idx64, const uint32_t* __restrict__ source, int64_t n)
 {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1170,14 +1203,19 @@ void cagra_search(resources& res, const cagra_index& idx, const cuvsCagraSearchP
   CUVS_EXPECTS(nq < (int64_t(1) << 24), "cagra::search: split the query batch (max 2^24 queries per call)");
   search_args a;
   a.data = idx.data; a.graph = idx.graph.data(); a.queries = queries; a.filter_bits = filter_bits;
+  a.source = idx.source_indices.data();
+  CUVS_EXPECTS(a.source == nullptr || (int64_t)idx.source_indices.size() == idx.n, "cagra::search: %zu source ids for %ld rows",
+               idx.source_indices.size(), (long)idx.n);
   a.out_idx = out_idx; a.out_dist = out_dist; a.n = idx.n; a.dim = idx.dim; a.degree = idx.degree;
   a.width = (uint32_t)std::max<size_t>(1, p.search_width);
   a.n_distill = (uint32_t)std::max<uint32_t>(1u, p.num_random_samplings);
   // share of rows the bitset removes: the reference derives it from the bitset's population count when the caller
-  // does not give one (cagra.cuh:374-381; the C search params have no such field) and widens the multi-CTA itopk
+  // does not give one (cagra.cuh:374-381; the C search params have no such field) and widens the multi-CTA itopk. The
+  // bitset is over source ids, so with a map the rows whose source bit is set are counted
   float filtering_rate = 0.f;
   if (filter_bits != nullptr) {
-    const int64_t kept = count_set_bits(res, filter_bits, idx.n);
+    const int64_t kept = a.source != nullptr ? count_kept_rows(res, filter_bits, a.source, idx.n)
+                                             : count_set_bits(res, filter_bits, idx.n);
     filtering_rate     = std::min(std::max((float)(idx.n - kept) / (float)idx.n, 0.0f), 0.999f);
   }
   const cagra_plan pl = make_cagra_plan(p, idx.n, idx.degree, (uint32_t)k, nq, res.num_cus, filtering_rate);
@@ -1256,7 +1294,7 @@ void cagra_search(resources& res, const cagra_index& idx, const cuvsCagraSearchP
     }
     if (idx.source_indices.data() != nullptr)
       hipLaunchKernelGGL(cagra_source_ids_kernel, dim3((unsigned)grid_blocks(nq * k, 256)), dim3(256), 0, res.stream, out_idx, nq * (int64_t)k,
-                         idx64 ? 1 : 0, idx.source_indices.data(), idx.n);
+                         idx64 ? 1 : 0, idx.source_indices.data(), (int64_t)idx.source_indices.size());
     return;
   }
   size_t smem = q_bytes + (size_t)a.np2 * 8 + ((size_t)4 << bits) +
@@ -1274,7 +1312,7 @@ void cagra_search(resources& res, const cagra_index& idx, const cuvsCagraSearchP
   }
   if (idx.source_indices.data() != nullptr)
     hipLaunchKernelGGL(cagra_source_ids_kernel, dim3((unsigned)grid_blocks(nq * k, 256)), dim3(256), 0, res.stream, out_idx, nq * (int64_t)k,
-                       idx64 ? 1 : 0, idx.source_indices.data(), idx.n);
+                       idx64 ? 1 : 0, idx.source_indices.data(), (int64_t)idx.source_indices.size());
 }
 
 // ------------------------------------------------------------------ extend (add_nodes.cuh)
@@ -1301,6 +1339,9 @@ __global__ void extend_rows_kernel(const uint32_t* __restrict__ nb, int64_t m, u
 
 void cagra_extend(resources& res, cagra_index& idx, const void* new_rows, bool new_is_host, int64_t m, uint32_t max_chunk)
 {
+  // the walk below reports source ids and the new rows would have none: the reference's add_nodes.cuh defines nothing for an
+  // index with source_indices, so it is refused before anything is touched
+  CUVS_EXPECTS(idx.source_indices.data() == nullptr, "cagra::extend: an index that carries source_indices cannot be extended");
   if (m == 0) return;
   CUVS_EXPECTS(idx.data != nullptr && idx.graph.data() != nullptr, "cagra::extend: index has no graph/dataset");
   CUVS_EXPECTS(idx.n + m < (int64_t(1) << 32) - 1, "cagra: at most 2^32 - 2 rows (uint32 graph)");
@@ -1475,6 +1516,15 @@ cagra_index& get_cagra(cuvsCagraIndex_t index)
 {
   CUVS_EXPECTS(index != nullptr && index->addr != 0, "CAGRA index is not built");
   return *reinterpret_cast<cagra_index*>(index->addr);
+}
+
+// a BITSET filter is read as ceil(n_bits / 32) words: refused on the host when the tensor is not 1-D or holds fewer
+void cagra_check_bitset(const DLTensor& ft, int64_t n_bits, const char* what)
+{
+  CUVS_EXPECTS(ft.ndim == 1 && is_c_contiguous(ft), "cagra: the bitset filter must be a 1-D contiguous tensor of uint32 words (got %d dimensions)",
+               (int)ft.ndim);
+  CUVS_EXPECTS(ft.shape[0] >= (n_bits + 31) / 32, "bitset filter holds %ld bits, the index %ld %s", (long)(ft.shape[0] * 32),
+               (long)n_bits, what);
 }
 }  // namespace
 
@@ -1683,6 +1733,9 @@ cuvsError_t cuvsCagraSearch(cuvsResources_t res_h, cuvsCagraSearchParams_t param
       CUVS_EXPECTS(filter.type == BITSET && filter.addr != 0, "cagra: only BITSET filters are supported");
       auto& ft = reinterpret_cast<DLManagedTensor*>(filter.addr)->dl_tensor;
       CUVS_EXPECTS(dtype_is(ft.dtype, kDLUInt, 32) && is_device_accessible(ft), "filter must be a device uint32 tensor");
+      // the bitset is over source ids: the rows themselves, or the image of the index's source_indices
+      cagra_check_bitset(ft, idx.source_indices.data() != nullptr ? idx.source_bits : idx.n,
+                         idx.source_indices.data() != nullptr ? "source ids" : "rows");
       bits = static_cast<const uint32_t*>(dl_data(ft));
     }
     cagra_search(res, idx, *params, dl_data(queries), m, (int)k, dl_data(neighbors), idx64,
@@ -1794,7 +1847,11 @@ cuvsError_t cuvsCagraDeserialize(cuvsResources_t res_h, const char* filename, cu
           idx->data  = idx->owned.data();
         }
       }
-      if (content & 2u) idx->source_indices = r.device_array<uint32_t>(res, idx->n);  // cagra_serialize.cuh:314-321
+      if (content & 2u) {  // cagra_serialize.cuh:314-321
+        idx->source_indices = r.device_array<uint32_t>(res, idx->n);
+        const std::vector<uint32_t> src = to_host(res, idx->source_indices.data(), (size_t)idx->n);
+        idx->source_bits = src.empty() ? 0 : (int64_t)*std::max_element(src.begin(), src.end()) + 1;
+      }
       dl = dl_of(idx->dtype);
     }
     cagra_set_norms(res, *idx);
@@ -1911,9 +1968,13 @@ cuvsError_t cuvsCagraMerge(cuvsResources_t res_h, cuvsCagraIndexParams_t params,
     for (size_t i = 0; i < num_indices; ++i) {
       auto& ix = get_cagra(indices[i]);
       CUVS_EXPECTS(ix.data != nullptr, "cagra::merge: index %zu has no dataset", i);
+      // the merged index numbers its rows by position in the concatenation, and the BITSET is over those positions: an input
+      // that reports source ids would be renumbered silently, so it is refused
+      CUVS_EXPECTS(ix.source_indices.data() == nullptr, "cagra::merge: index %zu carries source_indices and cannot be merged", i);
       CUVS_EXPECTS(ix.dim == first.dim && ix.dtype == first.dtype, "cagra::merge: indexes differ in dim or dtype");
       total += ix.n;
     }
+    if (filter.type == BITSET) cagra_check_bitset(reinterpret_cast<DLManagedTensor*>(filter.addr)->dl_tensor, total, "rows");
     const size_t row_bytes = (size_t)first.dim * elem_size(first.dtype);
     auto all = dev_buf<char>::persistent((size_t)total * row_bytes);
     size_t off = 0;

@@ -163,7 +163,8 @@ class _CExtendParams(C.Structure):
 @auto_sync_resources
 def extend(index, additional_dataset, max_chunk_size=0, resources=None):
     """cuvsCagraExtend: add rows to a built index (reference: python/cuvs/cuvs/neighbors/cagra extend). The index
-    owns its dataset afterwards."""
+    owns its dataset afterwards. An index loaded from a file that carries source_indices is refused: the new rows would have
+    no source id (the reference's add_nodes.cuh defines nothing for it)."""
     ds = additional_dataset.contiguous() if isinstance(additional_dataset, torch.Tensor) else np.ascontiguousarray(additional_dataset)
     p = C.POINTER(_CExtendParams)()
     check(lib().cuvsCagraExtendParamsCreate(C.byref(p)))
@@ -224,7 +225,13 @@ def from_graph(graph, dataset, metric="sqeuclidean", resources=None):
 
 @auto_sync_resources
 def search(search_params, index, queries, k, neighbors=None, distances=None, resources=None, filter=None):
-    """Returns (distances [m,k] float32, neighbors [m,k] uint32 stored in an int32 tensor, like the reference)."""
+    """Returns (distances [m,k] float32, neighbors [m,k] uint32 stored in an int32 tensor, like the reference).
+
+    filter: None or (words, BITSET): a 1-D device tensor of uint32 words, bit i = 1 keeps source id i. Source ids are the rows
+    themselves, or source_indices[row] for an index loaded from a file that carries them; the tensor must hold at least
+    n rows (max source id + 1 with a map) bits, a shorter one is refused. The single-workgroup walk filters when it writes its
+    results, so a filter that keeps few rows may return fewer than k neighbours: the missing slots are trailing padding, id
+    0xffffffff (-1 for int64 neighbors) at distance FLT_MAX. A larger itopk_size is the remedy."""
     if not index.trained:
         raise ValueError("Index needs to be built before calling search.")
     q = as_device(queries)
@@ -257,7 +264,9 @@ def load(filename, resources=None):
 @auto_sync_resources
 def merge(index_params, indices, resources=None, filter=None):
     """cuvsCagraMerge: one index over the concatenated datasets of `indices` (ids shifted by the preceding sizes); filter: None or a
-    bitset over the concatenated rows (uint32 words on the device, BITSET) - only rows whose bit is set are kept (cagra_merge.cuh:94-131)."""
+    bitset over the concatenated rows (1-D uint32 words on the device with at least one bit per row, BITSET) - only rows whose bit
+    is set are kept (cagra_merge.cuh:94-131). An input that carries source_indices is refused, not merged with its map dropped: the
+    merged index numbers rows by position in the concatenation, which would silently renumber what that input reports."""
     out = Index()
     arr = (C.POINTER(_CIndex) * len(indices))(*[ix._p for ix in indices])
     flt, keep = make_filter(filter)
