@@ -15,6 +15,7 @@
 #include <cuvs/neighbors/refine.h>
 #include <cuvs/neighbors/all_neighbors.h>
 #include <cuvs/neighbors/tiered_index.h>
+#include <cuvs/neighbors/vamana.h>
 #include <cuvs/preprocessing/pca.h>
 #include <cuvs/preprocessing/quantize/binary.h>
 #include <cuvs/preprocessing/quantize/pq.h>

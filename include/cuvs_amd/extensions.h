@@ -9,6 +9,7 @@
 #include <cuvs/neighbors/common.h>
 #include <cuvs/neighbors/ivf_pq.h>
 #include <cuvs/neighbors/tiered_index.h>
+#include <cuvs/neighbors/vamana.h>
 #include <cuvs/preprocessing/quantize/binary.h>
 #include <cuvs/preprocessing/quantize/pq.h>
 #include <stdint.h>
@@ -122,6 +123,30 @@ CUVS_EXPORT cuvsError_t cuvsAmdTieredMerge(cuvsResources_t res, DLManagedTensor*
 /* Launch counts since the library was loaded (the tests' proof of which path ran): out = {composed tail phases, single-launch tail
  * phases, single-launch tail phases redone because an append buffer overflowed}. */
 CUVS_EXPORT void cuvsAmdTieredCounters(unsigned long long out[3]);
+
+/* Vamana (cuvsVamana*). The reference's C ABI cannot read the graph back. cuvsAmdVamanaIndexGetGraph copies it
+ * into `out`, uint32 [n, graph_degree] on the host or the device (unused slots 0xFFFFFFFF, behind the used ones; the rows can
+ * be handed to cuvsCagraIndexFromArgs once those slots are replaced). cuvsAmdVamanaIndexGetMedoid: the entry node. */
+CUVS_EXPORT cuvsError_t cuvsAmdVamanaIndexGetGraph(cuvsResources_t res, cuvsVamanaIndex_t index, DLManagedTensor* out);
+CUVS_EXPORT cuvsError_t cuvsAmdVamanaIndexGetMedoid(cuvsVamanaIndex_t index, uint32_t* medoid);
+/* One launch of the build's search kernel on a GIVEN graph (how the tests pin the kernel to a restatement). All tensors on the
+ * device: dataset [n, dim] float32 / int8 / uint8, graph uint32 [n, params->graph_degree], query_ids uint32 [m] (rows of the
+ * dataset); out_ids uint32 / out_dists fp32 [m, visited_size] (visited_size after rounding) receive the expanded nodes of each
+ * walk from `medoid`, nearest first, without the query row itself, padded with 0xFFFFFFFF / FLT_MAX. */
+CUVS_EXPORT cuvsError_t cuvsAmdVamanaGreedySearch(cuvsResources_t res, cuvsVamanaIndexParams_t params, DLManagedTensor* dataset,
+                                                  DLManagedTensor* graph, uint32_t medoid, DLManagedTensor* query_ids,
+                                                  DLManagedTensor* out_ids, DLManagedTensor* out_dists);
+/* One launch of the build's prune kernel: for node_ids[i] the candidates cand_ids / cand_dists [m, visited_size] (padding
+ * 0xFFFFFFFF; cand_dists as cuvsAmdVamanaGreedySearch gives them) are merged with the node's row of `graph` and pruned to
+ * out_ids uint32 [m, graph_degree], padded with 0xFFFFFFFF. All tensors on the device; `graph` is not written. */
+CUVS_EXPORT cuvsError_t cuvsAmdVamanaRobustPrune(cuvsResources_t res, cuvsVamanaIndexParams_t params, DLManagedTensor* dataset,
+                                                 DLManagedTensor* graph, DLManagedTensor* node_ids, DLManagedTensor* cand_ids,
+                                                 DLManagedTensor* cand_dists, DLManagedTensor* out_ids);
+/* The sector-aligned SSD layout of DiskANN (the reference's C++ serialize(..., sector_aligned = true)): `<filename>_disk.index`
+ * holds a 4096-byte sector with the nine uint64 metadata words, then the nodes (row, uint32 count, ids) packed per sector, or one
+ * node over several sectors when it does not fit one. With include_dataset also `<filename>.data`. No PQ output. */
+CUVS_EXPORT cuvsError_t cuvsAmdVamanaSerializeSectorAligned(cuvsResources_t res, const char* filename, cuvsVamanaIndex_t index,
+                                                            bool include_dataset);
 
 /* Measurement helpers of bench.py (no reference counterpart). cuvsAmdProfileEnable / cuvsAmdProfileCollect: HIP events
  * around the named kernels on the handle's stream (Collect sums and resets the records of `name`, returns the launch count).

@@ -1,4 +1,4 @@
-// C++ surface over the C ABI: cuvs::neighbors::{brute_force, ivf_flat, ivf_pq, cagra}::build / search with the
+// C++ surface over the C ABI: cuvs::neighbors::{brute_force, ivf_flat, ivf_pq, cagra, vamana}::build / search with the
 // reference's names (cpp/include/cuvs/neighbors/{brute_force,ivf_flat,ivf_pq,cagra}.hpp). Header-only, C++17, no RAFT:
 // `raft::resources` -> cuvs::resources (RAII over cuvsResources_t), `raft::device_matrix_view<T, int64_t>` ->
 // cuvs::device_matrix_view<T> (data_handle(), extent(i) - the two members the reference call sites use). Parameter
@@ -411,6 +411,57 @@ void search(const resources& res, const search_params& p, const index<T>& idx, d
   check(cuvsCagraSearch(res.get(), cp.p, idx.get(), q.get(), n.get(), d.get(), none), "cuvsCagraSearch");
 }
 }  // namespace cagra
+
+namespace vamana {
+struct index_params {  // vamana.hpp: the C fields under the reference's C++ names and defaults
+  cuvsDistanceType metric    = L2Expanded;
+  uint32_t graph_degree      = 32;
+  uint32_t visited_size      = 64;
+  float vamana_iters         = 1.0f;
+  float alpha                = 1.2f;
+  float max_fraction         = 0.06f;
+  float batch_base           = 2.0f;
+  uint32_t queue_size        = 127;
+  uint32_t reverse_batchsize = 1000000;
+};
+template <typename T = float>
+class index {
+ public:
+  index() { check(cuvsVamanaIndexCreate(&h_), "cuvsVamanaIndexCreate"); }
+  ~index() { if (h_) cuvsVamanaIndexDestroy(h_); }
+  index(index&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  index(const index&) = delete;
+  cuvsVamanaIndex_t get() const { return h_; }
+  int dim() const { int v = 0; check(cuvsVamanaIndexGetDims(h_, &v), "cuvsVamanaIndexGetDims"); return v; }
+  uint32_t medoid() const { uint32_t v = 0; check(cuvsAmdVamanaIndexGetMedoid(h_, &v), "cuvsAmdVamanaIndexGetMedoid"); return v; }
+
+ private:
+  cuvsVamanaIndex_t h_ = nullptr;
+};
+// dataset: a device or a host view of float, int8_t or uint8_t rows; the index keeps its own device copy
+template <typename T>
+index<T> build(const resources& res, const index_params& p, device_matrix_view<const T> dataset)
+{
+  detail::c_params<cuvsVamanaIndexParams_t, cuvsVamanaIndexParamsCreate, cuvsVamanaIndexParamsDestroy> cp;
+  *cp.p = cuvsVamanaIndexParams{p.metric, p.graph_degree, p.visited_size, p.vamana_iters, p.alpha, p.max_fraction, p.batch_base,
+                                p.queue_size, p.reverse_batchsize};
+  index<T> idx;
+  detail::tensor<const T> d(dataset);
+  check(cuvsVamanaBuild(res.get(), cp.p, d.get(), idx.get()), "cuvsVamanaBuild");
+  return idx;
+}
+// vamana.hpp serialize(res, file_prefix, index, include_dataset, sector_aligned)
+template <typename T>
+void serialize(const resources& res, const std::string& file_prefix, const index<T>& idx, bool include_dataset = true,
+               bool sector_aligned = false)
+{
+  if (sector_aligned)
+    check(cuvsAmdVamanaSerializeSectorAligned(res.get(), file_prefix.c_str(), idx.get(), include_dataset),
+          "cuvsAmdVamanaSerializeSectorAligned");
+  else
+    check(cuvsVamanaSerialize(res.get(), file_prefix.c_str(), idx.get(), include_dataset), "cuvsVamanaSerialize");
+}
+}  // namespace vamana
 
 }  // namespace neighbors
 }  // namespace cuvs
