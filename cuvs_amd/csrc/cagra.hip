@@ -19,8 +19,10 @@
 #include "device_utils.hpp"
 #include "serialize.hpp"
 #include "npy_io.hpp"
+#include "pq_quantize.hpp"
 
 #include <cuvs/neighbors/cagra.h>
+#include <cuvs_amd/extensions.h>
 
 #include <algorithm>
 #include <type_traits>
@@ -28,6 +30,32 @@
 #include <cmath>
 
 namespace cuvs_amd {
+
+// A VPQ-compressed dataset: row i is vq_book[label_i] + pq_book[code_i[s]] per subspace s, both books fp16, one
+// PQ book shared by all subspaces, 8-bit codes. In memory a row is [uint32 label][8 x lane_bytes code bytes]: the codes that
+// lane t of an 8-lane team needs (the 4-element pieces at d = 4 t + 32 j, ascending j) are contiguous, lane after lane, each
+// lane's share padded with zeros to a multiple of 4 bytes. Files and cuvsAmdCagraIndexGetVpq show the reference's layout
+// [uint32 label][pq_dim code bytes][zero padding to 4].
+struct cagra_vpq {
+  uint32_t vq_n = 0, pq_len = 0, pq_dim = 0;
+  uint32_t row_len    = 0;  // bytes of a row in the reference's layout: 4 * (1 + ceil(pq_dim / 4))
+  uint32_t lane_bytes = 0;  // bytes of one lane's codes of a row
+  uint32_t stride     = 0;  // bytes of a row in memory: 4 + 8 * lane_bytes
+  dev_buf<__half> vq_book;  // [vq_n, dim]
+  dev_buf<__half> pq_book;  // [256, pq_len]
+  dev_buf<uint8_t> codes;   // [n, stride]
+  bool on() const { return codes.data() != nullptr; }
+  void set_shape(int64_t dim, uint32_t vq_centers, uint32_t len)
+  {
+    vq_n       = vq_centers;
+    pq_len     = len;
+    pq_dim     = (uint32_t)(dim / len);
+    row_len    = 4u * (1u + (pq_dim + 3u) / 4u);
+    lane_bytes = (uint32_t)round_up(((dim + 31) / 32) * (4 / len), 4);
+    stride     = 4u + 8u * lane_bytes;
+  }
+};
+constexpr uint32_t kVpqBookN = 256;  // entries of the PQ book (pq_bits = 8)
 
 struct cagra_index {
   int metric   = 0;
@@ -42,6 +70,7 @@ struct cagra_index {
   // bit 1, cagra_serialize.cuh:72-83): a search reports source_indices[row] instead of the row (search_multi_cta.cuh:266-272)
   dev_buf<uint32_t> source_indices;
   int64_t source_bits = 0;  // max(source_indices) + 1, found once at load: the bits a filter over source ids has to hold
+  cagra_vpq vpq;            // set: the rows are held compressed and `data` is null
 };
 
 // canonical row norms of the dataset for the cosine metric (no-op otherwise)
@@ -443,6 +472,11 @@ struct search_args {
   // with n_dist, n_iter MEASURED): [0] rows scored, [1] walk iterations (graph rows read), [2] walkers (waves). One atomic
   // per wave and counter at the end of the walk; nullptr: not counted.
   unsigned long long* work = nullptr;
+  // VPQ-compressed rows (cagra_vpq): `data` is null then
+  const uint8_t* codes  = nullptr;
+  const __half* vq_book = nullptr;
+  const __half* pq_book = nullptr;
+  uint32_t code_stride = 0, lane_words = 0;
 };
 
 // the filter is evaluated on the source id of a row (to_source_index, search_single_cta_jit.cuh:86-87,306-309)
@@ -609,6 +643,110 @@ __device__ inline uint32_t team_hamming(const uint8_t* __restrict__ data, int64_
   return n_scored;
 }
 
+// L2 distances of the nodes idx[first .. first+count) of a VPQ-compressed dataset to the query: team_distances<float> on the
+// decoded row x[d] = float(vq_book[label][d]) + float(pq_book[code[d / PL]][d % PL]) (one fp32 addition of two fp16 values),
+// same teams, same 4-element pieces at d = 4 t + 32 j, same order, same butterfly - so a search over the decoded fp32 rows
+// returns the same bits. Per row a lane reads the label, its own code bytes (contiguous in memory, 16 of them per load: 16
+// pieces at PL 4, 8 at PL 2), then per group of four pieces the four 8-byte pieces of the VQ centre (global memory; the table
+// is small and shared by all rows of a centre) and the PQ entries from the book staged in LDS (`book`: one 32-bit word per
+// entry at PL 2, two at PL 4).
+typedef uint32_t vpq_words4 __attribute__((ext_vector_type(4), aligned(4)));
+
+template <int PL>
+__device__ inline uint32_t team_vpq_distances(const search_args& a, const uint32_t* __restrict__ book, const float* __restrict__ qf,
+                                              uint32_t* __restrict__ keys, const uint32_t* __restrict__ idx, uint32_t first,
+                                              uint32_t count, int lane)
+{
+  static_assert(PL == 2 || PL == 4, "pq_len 2 or 4");
+  const int team = lane >> 3, tl = lane & 7;
+  const int64_t dim = a.dim;
+  const bool vec    = (dim & 3) == 0;  // the 4-element pieces of a VQ row are whole and 8-byte aligned
+  uint32_t n_scored = 0u;
+  for (uint32_t c0 = 0; c0 < count; c0 += 8) {
+    const uint32_t c    = c0 + team;
+    const uint32_t node = c < count ? (idx[first + c] & ~kParentFlag) : kInvalidNode;
+    const bool ok       = c < count && idx[first + c] != kInvalidNode;
+    n_scored += (uint32_t)__popcll(__ballot(ok && tl == 0));
+    float acc = 0.f;
+    if (ok) {
+      const uint8_t* row   = a.codes + (size_t)node * a.code_stride;
+      const uint32_t label = *reinterpret_cast<const uint32_t*>(row);
+      const uint32_t* cw   = reinterpret_cast<const uint32_t*>(row + 4) + (size_t)tl * a.lane_words;
+      const __half* vq     = a.vq_book + (size_t)label * dim;
+      // four pieces j0 .. j0 + 3 of this lane; cb: their code bytes, lowest first (4 bytes at PL 4, 8 at PL 2)
+      auto score4 = [&](const unsigned long long cb, const int64_t j0) {
+        uint2 v[4];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+          const int64_t d = 4 * tl + 32 * (j0 + p);
+          v[p]            = make_uint2(0u, 0u);
+          if (d < dim) {
+            if (vec) {
+              v[p] = *reinterpret_cast<const uint2*>(vq + d);
+            } else {
+              __half* h = reinterpret_cast<__half*>(&v[p]);
+#pragma unroll
+              for (int e = 0; e < 4; ++e)
+                if (d + e < dim) h[e] = vq[d + e];
+            }
+          }
+        }
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+          const int64_t d = 4 * tl + 32 * (j0 + p);
+          if (d < dim) {
+            uint2 b;
+            if constexpr (PL == 4) {
+              b = *reinterpret_cast<const uint2*>(book + 2u * (uint32_t)((cb >> (8 * p)) & 255u));
+            } else {
+              b.x = book[(uint32_t)((cb >> (16 * p)) & 255u)];
+              b.y = book[(uint32_t)((cb >> (16 * p + 8)) & 255u)];
+            }
+            const __half* vh = reinterpret_cast<const __half*>(&v[p]);
+            const __half* bh = reinterpret_cast<const __half*>(&b);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              if (d + e < dim) {
+                const float x = __half2float(vh[e]) + __half2float(bh[e]);
+                const float s = x - qf[d + e];
+                acc           = __fmaf_rn(s, s, acc);
+              }
+            }
+          }
+        }
+      };
+      for (uint32_t w0 = 0; w0 < a.lane_words; w0 += 4) {
+        uint32_t w[4];
+        if (w0 + 4 <= a.lane_words) {
+          const vpq_words4 t = *reinterpret_cast<const vpq_words4*>(cw + w0);
+          w[0] = t.x; w[1] = t.y; w[2] = t.z; w[3] = t.w;
+        } else {
+#pragma unroll
+          for (int u = 0; u < 4; ++u) w[u] = w0 + u < a.lane_words ? cw[w0 + u] : 0u;
+        }
+        if constexpr (PL == 4) {
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+            if (w0 + u < a.lane_words) score4(w[u], (int64_t)(w0 + u) * 4);
+        } else {
+#pragma unroll
+          for (int u = 0; u < 4; u += 2)
+            if (w0 + u < a.lane_words) score4((unsigned long long)w[u] | ((unsigned long long)w[u + 1] << 32), (int64_t)(w0 + u) * 2);
+        }
+      }
+    }
+    acc = acc + __shfl_xor(acc, 1, kWave);
+    acc = acc + __shfl_xor(acc, 2, kWave);
+    acc = acc + __shfl_xor(acc, 4, kWave);
+    if (tl == 0 && c < count) keys[first + c] = ok ? float_to_key(acc) : 0xffffffffu;
+  }
+  return n_scored;
+}
+
+// 32-bit words of LDS that hold the PQ book of a compressed dataset: fp16 [256, PL]
+template <int PL>
+__host__ __device__ constexpr uint32_t vpq_book_words() { return kVpqBookN * PL / 2; }
+
 // 32-bit words of LDS that hold the query: fp32 elements, or (BitwiseHamming) bytes padded to 16
 template <bool HAM>
 __host__ __device__ inline int64_t query_words(int64_t dim)
@@ -626,15 +764,18 @@ __device__ inline float wave_query_norm(const float* qf, int64_t dim, int lane)
 }
 
 // HAM: BitwiseHamming over the bytes of uint8 / int8 rows (T = uint8_t), the query staged as bytes
-template <typename T, bool HAM = false>
+// PL != 0: a VPQ-compressed dataset with this pq_len (T: the dtype of the queries); the PQ book sits in front of the query
+template <typename T, bool HAM = false, int PL = 0>
 __global__ __launch_bounds__(64) void cagra_search_kernel(search_args a)
 {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane   = threadIdx.x;
   const int64_t qi = blockIdx.x;
-  float* qf        = reinterpret_cast<float*>(smem);
+  constexpr uint32_t kBook = vpq_book_words<PL>();
+  uint32_t* book   = reinterpret_cast<uint32_t*>(smem);
+  float* qf        = reinterpret_cast<float*>(smem) + kBook;
   uint8_t* qb      = reinterpret_cast<uint8_t*>(smem);
-  uint32_t* keys   = reinterpret_cast<uint32_t*>(smem) + query_words<HAM>(a.dim);
+  uint32_t* keys   = reinterpret_cast<uint32_t*>(smem) + kBook + query_words<HAM>(a.dim);
   uint32_t* idx    = keys + a.np2;
   uint32_t* table  = idx + a.np2;
   const uint32_t hsize = 1u << a.hash_bits;
@@ -645,6 +786,8 @@ __global__ __launch_bounds__(64) void cagra_search_kernel(search_args a)
   } else {
     for (int64_t d = lane; d < a.dim; d += 64) qf[d] = to_float(static_cast<const T*>(a.queries)[qi * a.dim + d]);
   }
+  if constexpr (PL != 0)
+    for (uint32_t i = lane; i < kBook; i += 64) book[i] = reinterpret_cast<const uint32_t*>(a.pq_book)[i];
   for (uint32_t i = lane; i < a.np2; i += 64) { keys[i] = 0xffffffffu; idx[i] = kInvalidNode; }
   for (uint32_t i = lane; i < hsize; i += 64) table[i] = kInvalidNode;
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -670,7 +813,8 @@ __global__ __launch_bounds__(64) void cagra_search_kernel(search_args a)
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    if constexpr (HAM) n_dist += team_hamming(reinterpret_cast<const uint8_t*>(data), a.dim, qb, tkeys, tidx, 0, n_seed, lane);
+    if constexpr (PL != 0) n_dist += team_vpq_distances<PL>(a, book, qf, tkeys, tidx, 0, n_seed, lane);
+    else if constexpr (HAM) n_dist += team_hamming(reinterpret_cast<const uint8_t*>(data), a.dim, qb, tkeys, tidx, 0, n_seed, lane);
     else               n_dist += team_distances<T>(data, a.dim, qf, tkeys, tidx, 0, n_seed, a.is_ip, lane, a.norms, qn);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -731,7 +875,8 @@ __global__ __launch_bounds__(64) void cagra_search_kernel(search_args a)
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    if constexpr (HAM) n_dist += team_hamming(reinterpret_cast<const uint8_t*>(data), a.dim, qb, keys, idx, a.itopk, n_cand, lane);
+    if constexpr (PL != 0) n_dist += team_vpq_distances<PL>(a, book, qf, keys, idx, a.itopk, n_cand, lane);
+    else if constexpr (HAM) n_dist += team_hamming(reinterpret_cast<const uint8_t*>(data), a.dim, qb, keys, idx, a.itopk, n_cand, lane);
     else               n_dist += team_distances<T>(data, a.dim, qf, keys, idx, a.itopk, n_cand, a.is_ip, lane, a.norms, qn);
     n_rows_read += n_parents;
     ++iter;
@@ -821,7 +966,7 @@ __device__ inline void trav_remove(uint32_t* table, uint32_t bits, uint32_t key)
   }
 }
 
-template <typename T, bool HAM = false>
+template <typename T, bool HAM = false, int PL = 0>
 __global__ __launch_bounds__(1024) void cagra_search_multi_kernel(mw_args m)
 {
   const search_args& a = m.s;
@@ -830,9 +975,11 @@ __global__ __launch_bounds__(1024) void cagra_search_multi_kernel(mw_args m)
   const int wave   = threadIdx.x >> 6;
   const int64_t qi = blockIdx.x;
   const uint32_t W = m.n_waves, np2 = m.np2_local, vsize = 1u << m.vis_bits, tsize = 1u << m.trav_bits;
-  float* qf        = reinterpret_cast<float*>(smem);
+  constexpr uint32_t kBook = vpq_book_words<PL>();
+  uint32_t* book   = reinterpret_cast<uint32_t*>(smem);
+  float* qf        = reinterpret_cast<float*>(smem) + kBook;
   uint8_t* qb      = reinterpret_cast<uint8_t*>(smem);
-  uint32_t* trav   = reinterpret_cast<uint32_t*>(smem) + query_words<HAM>(a.dim);
+  uint32_t* trav   = reinterpret_cast<uint32_t*>(smem) + kBook + query_words<HAM>(a.dim);
   uint32_t* mkeys  = trav + tsize;             // merge area [merge_np2]
   uint32_t* midx   = mkeys + m.merge_np2;
   uint32_t* wbase  = midx + m.merge_np2 + (size_t)wave * (2 * np2 + vsize);
@@ -847,6 +994,8 @@ __global__ __launch_bounds__(1024) void cagra_search_multi_kernel(mw_args m)
   } else {
     for (int64_t d = threadIdx.x; d < a.dim; d += blockDim.x) qf[d] = to_float(static_cast<const T*>(a.queries)[qi * a.dim + d]);
   }
+  if constexpr (PL != 0)
+    for (uint32_t i = threadIdx.x; i < kBook; i += blockDim.x) book[i] = reinterpret_cast<const uint32_t*>(a.pq_book)[i];
   for (uint32_t i = threadIdx.x; i < tsize; i += blockDim.x) trav[i] = kInvalidNode;
   for (uint32_t i = lane; i < np2; i += 64) { keys[i] = 0xffffffffu; idx[i] = kInvalidNode; }
   for (uint32_t i = lane; i < vsize; i += 64) vis[i] = kInvalidNode;
@@ -869,7 +1018,8 @@ __global__ __launch_bounds__(1024) void cagra_search_multi_kernel(mw_args m)
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       __builtin_amdgcn_wave_barrier();
-      if constexpr (HAM) n_dist += team_hamming(reinterpret_cast<const uint8_t*>(data), a.dim, qb, tkeys, tidx, 0, n_seed, lane);
+      if constexpr (PL != 0) n_dist += team_vpq_distances<PL>(a, book, qf, tkeys, tidx, 0, n_seed, lane);
+      else if constexpr (HAM) n_dist += team_hamming(reinterpret_cast<const uint8_t*>(data), a.dim, qb, tkeys, tidx, 0, n_seed, lane);
       else               n_dist += team_distances<T>(data, a.dim, qf, tkeys, tidx, 0, n_seed, a.is_ip, lane, a.norms, qn);
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       __builtin_amdgcn_wave_barrier();
@@ -960,7 +1110,8 @@ __global__ __launch_bounds__(1024) void cagra_search_multi_kernel(mw_args m)
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    if constexpr (HAM) n_dist += team_hamming(reinterpret_cast<const uint8_t*>(data), a.dim, qb, keys, idx, kMwTopk, a.degree, lane);
+    if constexpr (PL != 0) n_dist += team_vpq_distances<PL>(a, book, qf, keys, idx, kMwTopk, a.degree, lane);
+    else if constexpr (HAM) n_dist += team_hamming(reinterpret_cast<const uint8_t*>(data), a.dim, qb, keys, idx, kMwTopk, a.degree, lane);
     else               n_dist += team_distances<T>(data, a.dim, qf, keys, idx, kMwTopk, a.degree, a.is_ip, lane, a.norms, qn);
     n_rows_read += parent != kInvalidNode ? 1u : 0u;
     // ---- drop what another wave has expanded meanwhile; a parent that fails the filter leaves the list
@@ -1013,10 +1164,10 @@ __global__ __launch_bounds__(1024) void cagra_search_multi_kernel(mw_args m)
   }
 }
 
-template <typename T, bool HAM = false>
+template <typename T, bool HAM = false, int PL = 0>
 void launch_search_multi(resources& res, const mw_args& m, int64_t nq, size_t smem)
 {
-  auto kern = cagra_search_multi_kernel<T, HAM>;
+  auto kern = cagra_search_multi_kernel<T, HAM, PL>;
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
   profile_begin(res, "cagra_search_multi_kernel");
   hipLaunchKernelGGL(kern, dim3((unsigned)nq), dim3(64 * m.n_waves), smem, res.stream, m);
@@ -1024,15 +1175,27 @@ void launch_search_multi(resources& res, const mw_args& m, int64_t nq, size_t sm
   HIP_TRY(hipGetLastError());
 }
 
-template <typename T, bool HAM = false>
+template <typename T, bool HAM = false, int PL = 0>
 void launch_search(resources& res, const search_args& a, int64_t nq, size_t smem)
 {
-  auto kern = cagra_search_kernel<T, HAM>;
+  auto kern = cagra_search_kernel<T, HAM, PL>;
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
   profile_begin(res, "cagra_search_kernel");
   hipLaunchKernelGGL(kern, dim3((unsigned)nq), dim3(64), smem, res.stream, a);
   profile_end(res, "cagra_search_kernel");
   HIP_TRY(hipGetLastError());
+}
+
+// the walks over a VPQ-compressed dataset: T is the dtype of the queries
+template <int PL>
+void launch_search_vpq(resources& res, elem_t qt, const search_args& a, const mw_args* m, int64_t nq, size_t smem)
+{
+  switch (qt) {
+    case elem_t::f32: m ? launch_search_multi<float, false, PL>(res, *m, nq, smem) : launch_search<float, false, PL>(res, a, nq, smem); break;
+    case elem_t::f16: m ? launch_search_multi<__half, false, PL>(res, *m, nq, smem) : launch_search<__half, false, PL>(res, a, nq, smem); break;
+    case elem_t::i8: m ? launch_search_multi<int8_t, false, PL>(res, *m, nq, smem) : launch_search<int8_t, false, PL>(res, a, nq, smem); break;
+    case elem_t::u8: m ? launch_search_multi<uint8_t, false, PL>(res, *m, nq, smem) : launch_search<uint8_t, false, PL>(res, a, nq, smem); break;
+  }
 }
 
 }  // namespace
@@ -1198,12 +1361,18 @@ void cagra_search(resources& res, const cagra_index& idx, const cuvsCagraSearchP
                   int64_t nq, int k, void* out_idx, bool idx64, float* out_dist, const uint32_t* filter_bits)
 {
   if (nq == 0) return;
-  CUVS_EXPECTS(idx.graph.data() != nullptr && idx.data != nullptr, "cagra index has no graph/dataset");
+  const bool vpq = idx.vpq.on();
+  CUVS_EXPECTS(idx.graph.data() != nullptr && (idx.data != nullptr || vpq), "cagra index has no graph/dataset");
   CUVS_EXPECTS(k >= 1, "k must be positive");
   CUVS_EXPECTS(nq < (int64_t(1) << 24), "cagra::search: split the query batch (max 2^24 queries per call)");
   search_args a;
   a.data = idx.data; a.graph = idx.graph.data(); a.queries = queries; a.filter_bits = filter_bits;
   a.source = idx.source_indices.data();
+  if (vpq) {
+    CUVS_EXPECTS(idx.metric == M_L2Expanded, "VPQ compression is only supported with L2Expanded distance mertric");
+    a.codes = idx.vpq.codes.data(); a.vq_book = idx.vpq.vq_book.data(); a.pq_book = idx.vpq.pq_book.data();
+    a.code_stride = idx.vpq.stride; a.lane_words = idx.vpq.lane_bytes / 4;
+  }
   CUVS_EXPECTS(a.source == nullptr || (int64_t)idx.source_indices.size() == idx.n, "cagra::search: %zu source ids for %ld rows",
                idx.source_indices.size(), (long)idx.n);
   a.out_idx = out_idx; a.out_dist = out_dist; a.n = idx.n; a.dim = idx.dim; a.degree = idx.degree;
@@ -1240,7 +1409,9 @@ void cagra_search(resources& res, const cagra_index& idx, const cuvsCagraSearchP
   const bool ham = idx.metric == M_BitwiseHamming;
   CUVS_EXPECTS(!ham || idx.dtype == elem_t::u8 || idx.dtype == elem_t::i8,
                "BitwiseHamming distance is only supported for int8_t and uint8_t data types. Current data type is not supported.");
-  const size_t q_bytes = (size_t)(ham ? query_words<true>(idx.dim) : query_words<false>(idx.dim)) * 4;
+  // (a compressed index: the fp16 PQ book, 1 or 2 KB, in front of the query; 16-byte aligned by its size)
+  const size_t q_bytes = (size_t)(ham ? query_words<true>(idx.dim) : query_words<false>(idx.dim)) * 4 +
+                         (vpq ? (size_t)kVpqBookN * idx.vpq.pq_len * sizeof(__half) : 0);
   a.is_ip          = ham ? 3 : (idx.metric == M_InnerProduct ? 1 : (idx.metric == M_CosineExpanded ? 2 : 0));
   a.norms          = idx.norms.data();
   a.work           = res.cagra_work;
@@ -1282,7 +1453,10 @@ void cagra_search(resources& res, const cagra_index& idx, const cuvsCagraSearchP
     size_t msmem = q_bytes + ((size_t)4 << m.trav_bits) + (size_t)m.merge_np2 * 8 +
                    (size_t)W * (2 * m.np2_local + (1u << m.vis_bits)) * 4 + (size_t)W * 2 * idx.degree * 4;
     CUVS_EXPECTS(msmem <= 160 * 1024, "cagra::search: dim too large for the multi-wave LDS layout");
-    if (ham) {
+    if (vpq) {
+      if (idx.vpq.pq_len == 4) launch_search_vpq<4>(res, idx.dtype, a, &m, nq, msmem);
+      else                     launch_search_vpq<2>(res, idx.dtype, a, &m, nq, msmem);
+    } else if (ham) {
       launch_search_multi<uint8_t, true>(res, m, nq, msmem);
     } else {
       switch (idx.dtype) {
@@ -1300,7 +1474,10 @@ void cagra_search(resources& res, const cagra_index& idx, const cuvsCagraSearchP
   size_t smem = q_bytes + (size_t)a.np2 * 8 + ((size_t)4 << bits) +
                 (size_t)(2 * (itopk + a.width * idx.degree) + a.width) * 4;  // + seed candidates, parent list
   CUVS_EXPECTS(smem <= 160 * 1024, "cagra::search: dim/itopk too large for LDS");
-  if (ham) {
+  if (vpq) {
+    if (idx.vpq.pq_len == 4) launch_search_vpq<4>(res, idx.dtype, a, nullptr, nq, smem);
+    else                     launch_search_vpq<2>(res, idx.dtype, a, nullptr, nq, smem);
+  } else if (ham) {
     launch_search<uint8_t, true>(res, a, nq, smem);
   } else {
     switch (idx.dtype) {
@@ -1457,11 +1634,263 @@ void cagra_check_build(const cuvsCagraIndexParams& p, elem_t et)
                "BitwiseHamming distance is only supported for int8_t and uint8_t data types. Current data type is not supported.");
 }
 
+// ------------------------------------------------------------------ VPQ compression
+// position of subspace s's code among the 8 * lane_bytes code bytes of a row in memory (cagra_vpq)
+__host__ __device__ inline uint32_t vpq_code_pos(uint32_t s, uint32_t pq_len, uint32_t lane_bytes)
+{
+  if (pq_len == 4) return (s & 7u) * lane_bytes + (s >> 3);          // lane s % 8, piece s / 8
+  return ((s & 15u) >> 1) * lane_bytes + 2u * (s >> 4) + (s & 1u);   // lane (s % 16) / 2, piece s / 16, its two codes in order
+}
+
+// rows in memory from labels (a uint32 every label_pitch bytes) and codes (pq_dim bytes every code_pitch bytes): a thread per
+// byte of the output
+__global__ void vpq_pack_kernel(const uint8_t* __restrict__ labels, size_t label_pitch, const uint8_t* __restrict__ codes,
+                                size_t code_pitch, int64_t n, uint32_t pq_dim, uint32_t pq_len, uint32_t lane_bytes,
+                                uint8_t* __restrict__ out)
+{
+  const uint32_t stride = 4u + 8u * lane_bytes;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n * stride; t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r  = t / stride;
+    const uint32_t b = (uint32_t)(t - r * stride);
+    uint8_t v        = 0;
+    if (b < 4) {
+      v = labels[(size_t)r * label_pitch + b];
+    } else {
+      const uint32_t lane = (b - 4) / lane_bytes, k = (b - 4) % lane_bytes;
+      const uint32_t sub  = pq_len == 4 ? lane + 8u * k : 2u * lane + 16u * (k >> 1) + (k & 1u);
+      if (sub < pq_dim) v = codes[(size_t)r * code_pitch + sub];
+    }
+    out[t] = v;
+  }
+}
+
+// rows r0 .. r0 + n in the reference's layout [n, row_len] from the rows in memory: a thread per byte of the output
+__global__ void vpq_unpack_kernel(const uint8_t* __restrict__ mem, int64_t n, uint32_t pq_dim, uint32_t pq_len, uint32_t lane_bytes,
+                                  uint32_t row_len, uint8_t* __restrict__ out)
+{
+  const uint32_t stride = 4u + 8u * lane_bytes;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n * row_len; t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r  = t / row_len;
+    const uint32_t b = (uint32_t)(t - r * row_len);
+    const uint8_t* m = mem + (size_t)r * stride;
+    out[t]           = b < 4 ? m[b] : (b - 4 < pq_dim ? m[4 + vpq_code_pos(b - 4, pq_len, lane_bytes)] : (uint8_t)0);
+  }
+}
+
+// the largest label of rows in the reference's layout (an untrusted file: a label indexes the VQ table)
+__global__ void vpq_max_label_kernel(const uint8_t* __restrict__ rows, int64_t n, uint32_t row_len, uint32_t* __restrict__ out)
+{
+  uint32_t mx = 0;
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x)
+    mx = max(mx, *reinterpret_cast<const uint32_t*>(rows + (size_t)r * row_len));
+  for (int off = 32; off > 0; off >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, off, 64));
+  if ((threadIdx.x & 63) == 0) atomicMax(out, mx);
+}
+
+// fp32 -> fp16 (round to nearest even); `rounded` (optional, may be `x`) receives the rounded values as fp32
+__global__ void vpq_round_book_kernel(const float* x, int64_t n, __half* __restrict__ out, float* rounded)
+{
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const __half h = __float2half_rn(x[i]);
+  out[i]         = h;
+  if (rounded != nullptr) rounded[i] = __half2float(h);
+}
+void vpq_round_book(resources& res, const float* x, int64_t n, __half* out, float* rounded)
+{
+  hipLaunchKernelGGL(vpq_round_book_kernel, dim3(grid_blocks(n, 256)), dim3(256), 0, res.stream, x, n, out, rounded);
+  HIP_TRY(hipGetLastError());
+}
+
+inline unsigned vpq_grid(const resources& res, int64_t items) { return (unsigned)std::min<int64_t>((items + 255) / 256, (int64_t)res.num_cus * 32); }
+
+constexpr int64_t kVpqIoBytes = int64_t(64) << 20;  // rows in the reference's layout pass through buffers of this size
+
+// The rows of a file (the reference's layout, delivered by `read(host buffer, bytes)` in order) become the index's codes, a
+// chunk at a time: neither the file's rows nor a second copy of the dataset is ever resident. The file is untrusted: a label
+// outside the VQ table is refused (one device reduction per chunk), and the half-filled index is dropped by the caller.
+template <typename Read>
+void vpq_load_rows(resources& res, cagra_index& idx, Read&& read)
+{
+  auto& v = idx.vpq;
+  CUVS_EXPECTS(idx.n > 0, "cagra::deserialize: the VPQ dataset holds no rows");
+  const int64_t step = std::max<int64_t>(1, kVpqIoBytes / v.row_len);
+  v.codes = dev_buf<uint8_t>::persistent((size_t)idx.n * v.stride);
+  dev_buf<uint8_t> rows(res, (size_t)std::min(step, idx.n) * v.row_len);
+  dev_buf<uint32_t> mx(res, 1);
+  std::vector<uint8_t> h(rows.size());
+  for (int64_t r0 = 0; r0 < idx.n; r0 += step) {
+    const int64_t cnt = std::min(step, idx.n - r0);
+    read(h.data(), (size_t)cnt * v.row_len);
+    copy_async(res, rows.data(), h.data(), (size_t)cnt * v.row_len);
+    HIP_TRY(hipMemsetAsync(mx.data(), 0, sizeof(uint32_t), res.stream));
+    hipLaunchKernelGGL(vpq_max_label_kernel, dim3(vpq_grid(res, cnt)), dim3(256), 0, res.stream, rows.data(), cnt, v.row_len, mx.data());
+    hipLaunchKernelGGL(vpq_pack_kernel, dim3(vpq_grid(res, cnt * (int64_t)v.stride)), dim3(256), 0, res.stream, rows.data(),
+                       (size_t)v.row_len, rows.data() + 4, (size_t)v.row_len, cnt, v.pq_dim, v.pq_len, v.lane_bytes,
+                       v.codes.data() + (size_t)r0 * v.stride);
+    HIP_TRY(hipGetLastError());
+    const uint32_t top = read_word(res, mx.data());  // (also: the host buffer is free again)
+    CUVS_EXPECTS(top < v.vq_n, "cagra: the VPQ dataset holds the VQ label %u, the VQ codebook has %u centres", top, v.vq_n);
+  }
+}
+
+// rows r0 .. r0 + cnt of a compressed index in the reference's layout, into `out` (device)
+void vpq_export_rows(resources& res, const cagra_index& idx, int64_t r0, int64_t cnt, uint8_t* out)
+{
+  const auto& v = idx.vpq;
+  if (cnt == 0) return;
+  hipLaunchKernelGGL(vpq_unpack_kernel, dim3(vpq_grid(res, cnt * (int64_t)v.row_len)), dim3(256), 0, res.stream,
+                     v.codes.data() + (size_t)r0 * v.stride, cnt, v.pq_dim, v.pq_len, v.lane_bytes, v.row_len, out);
+  HIP_TRY(hipGetLastError());
+}
+
+// all rows of a compressed index in the reference's layout, handed to `write(host buffer, bytes)` a chunk at a time
+template <typename Write>
+void vpq_store_rows(resources& res, const cagra_index& idx, Write&& write)
+{
+  const auto& v = idx.vpq;
+  const int64_t step = std::max<int64_t>(1, kVpqIoBytes / v.row_len);
+  dev_buf<uint8_t> rows(res, (size_t)std::min(step, idx.n) * v.row_len);
+  std::vector<uint8_t> h(rows.size());
+  for (int64_t r0 = 0; r0 < idx.n; r0 += step) {
+    const int64_t cnt = std::min(step, idx.n - r0);
+    vpq_export_rows(res, idx, r0, cnt, rows.data());
+    copy_async(res, h.data(), rows.data(), (size_t)cnt * v.row_len);
+    sync(res);
+    write(h.data(), (size_t)cnt * v.row_len);
+  }
+}
+
+// The parameters a compressed build runs with: the zero fields filled by the reference's heuristics
+// (vpq_dataset.cuh:124-144), the train-set sizes of make_pq_params_from_vpq (pq.cuh:385-407). Host only; refuses what the
+// search over codes does not serve.
+struct vpq_plan {
+  uint32_t pq_dim, pq_len, vq_n, n_iters, max_pq, max_vq;
+  int64_t n_train, n_vq_train;
+};
+vpq_plan cagra_vpq_plan(const cuvsCagraIndexParams& p, int64_t n, int64_t dim)
+{
+  const cuvsCagraCompressionParams& c = *p.compression;
+  CUVS_EXPECTS((int)p.metric == M_L2Expanded, "VPQ compression is only supported with L2Expanded distance mertric");
+  CUVS_EXPECTS(dim > 0 && n > 0, "cagra: empty dataset");
+  vpq_plan pl{};
+  const uint32_t pq_bits = c.pq_bits == 0 ? 8u : c.pq_bits;
+  CUVS_EXPECTS(pq_bits == 8, "cagra: VPQ compression supports pq_bits = 8 only (got %u)", pq_bits);
+  pl.pq_dim = c.pq_dim == 0 ? (uint32_t)((dim + 3) / 4) : c.pq_dim;
+  CUVS_EXPECTS(dim % pl.pq_dim == 0, "cagra: VPQ compression needs dim (%ld) to be a multiple of pq_dim (%u)", (long)dim, pl.pq_dim);
+  pl.pq_len = (uint32_t)(dim / pl.pq_dim);
+  CUVS_EXPECTS(pl.pq_len == 2 || pl.pq_len == 4, "cagra: VPQ compression supports pq_len = dim / pq_dim of 2 or 4 only (got %u)", pl.pq_len);
+  CUVS_EXPECTS(n >= (int64_t)kVpqBookN, "cagra: VPQ compression needs at least 256 rows to train the PQ codebook (got %ld)", (long)n);
+  pl.vq_n = c.vq_n_centers == 0 ? (uint32_t)round_up((int64_t)(uint32_t)std::sqrt((double)n), 8) : c.vq_n_centers;
+  CUVS_EXPECTS((int64_t)pl.vq_n <= n, "cagra: vq_n_centers (%u) exceeds the number of rows (%ld)", pl.vq_n, (long)n);
+  pl.n_iters = c.kmeans_n_iters;
+  CUVS_EXPECTS(pl.n_iters > 0, "cagra: kmeans_n_iters of the compression parameters must be positive");
+  const double vq_frac = c.vq_kmeans_trainset_fraction == 0 ? std::min(1.0, 100.0 * pl.vq_n / (double)n) : c.vq_kmeans_trainset_fraction;
+  const double pq_frac = c.pq_kmeans_trainset_fraction == 0 ? std::min(1.0, 1000.0 * kVpqBookN / (double)n) : c.pq_kmeans_trainset_fraction;
+  CUVS_EXPECTS(vq_frac > 0 && vq_frac <= 1 && pq_frac > 0 && pq_frac <= 1, "cagra: the k-means trainset fractions of the compression parameters must be in (0, 1]");
+  pl.max_vq     = (uint32_t)std::min<double>(1024.0, (double)n * vq_frac / pl.vq_n);
+  pl.max_pq     = (uint32_t)std::min<double>(256.0, (double)n * pq_frac / kVpqBookN);
+  pl.n_train    = std::min<int64_t>(n, (int64_t)pl.max_pq * kVpqBookN);
+  pl.n_vq_train = std::min<int64_t>(n, (int64_t)pl.max_vq * pl.vq_n);
+  CUVS_EXPECTS(pl.n_train >= (int64_t)kVpqBookN,
+               "cagra: the PQ training set of VPQ compression holds %ld rows, at least 256 are needed (pq_kmeans_trainset_fraction)",
+               (long)pl.n_train);
+  CUVS_EXPECTS(pl.n_vq_train >= (int64_t)pl.vq_n,
+               "cagra: the VQ training set of VPQ compression holds %ld rows, vq_n_centers (%u) are needed (vq_kmeans_trainset_fraction)",
+               (long)pl.n_vq_train, pl.vq_n);
+  return pl;
+}
+
+// device rows of any dtype -> fp32 [m, dim]: every row_step-th row from `src` on
+void vpq_rows_to_float(resources& res, const void* src, elem_t et, int64_t row_step, int64_t m, int64_t dim, float* out,
+                       dev_buf<char>& staging)
+{
+  const size_t row_bytes = (size_t)dim * elem_size(et);
+  const void* packed     = src;
+  if (row_step > 1 || et == elem_t::f32) {
+    void* dst = et == elem_t::f32 ? static_cast<void*>(out) : static_cast<void*>(staging.data());
+    HIP_TRY(hipMemcpy2DAsync(dst, row_bytes, src, row_bytes * (size_t)row_step, row_bytes, (size_t)m, hipMemcpyDefault, res.stream));
+    packed = dst;
+  }
+  const int64_t cnt = m * dim;
+  switch (et) {
+    case elem_t::f32: break;
+    case elem_t::f16:
+      hipLaunchKernelGGL((to_float_kernel<__half>), dim3(grid_blocks(cnt, 256)), dim3(256), 0, res.stream, static_cast<const __half*>(packed), cnt, out);
+      break;
+    case elem_t::i8:
+      hipLaunchKernelGGL((to_float_kernel<int8_t>), dim3(grid_blocks(cnt, 256)), dim3(256), 0, res.stream, static_cast<const int8_t*>(packed), cnt, out);
+      break;
+    case elem_t::u8:
+      hipLaunchKernelGGL((to_float_kernel<uint8_t>), dim3(grid_blocks(cnt, 256)), dim3(256), 0, res.stream, static_cast<const uint8_t*>(packed), cnt, out);
+      break;
+  }
+  HIP_TRY(hipGetLastError());
+}
+
+// vpq_build restated (pq.cuh:409-442) over the device rows of `idx`: trains the VQ centres and the shared PQ book on strided
+// subsamples, rounds both books to fp16 and encodes every row AGAINST THE ROUNDED BOOKS (the reference encodes against the
+// fp32 books and rounds afterwards: here the codes are the best ones for the values the search reads). Rows pass through fp32
+// a chunk at a time; the original rows are dropped at the end.
+void cagra_compress(resources& res, cagra_index& idx, const vpq_plan& pl)
+{
+  const int64_t n = idx.n, dim = idx.dim;
+  const size_t esz = elem_size(idx.dtype);
+  auto& v = idx.vpq;
+  v.set_shape(dim, pl.vq_n, pl.pq_len);
+  std::unique_ptr<product_quantizer> q;
+  {
+    const int64_t m = std::max(pl.n_train, pl.n_vq_train);  // one strided subsample holds both train sets
+    dev_buf<float> train(res, (size_t)(m * dim));
+    dev_buf<char> staging;
+    if (idx.dtype != elem_t::f32) staging = dev_buf<char>(res, (size_t)m * dim * esz);
+    vpq_rows_to_float(res, idx.data, idx.dtype, n / m, m, dim, train.data(), staging);
+    cuvsProductQuantizerParams qp{};
+    qp.pq_bits = 8; qp.pq_dim = pl.pq_dim; qp.use_subspaces = false; qp.use_vq = true; qp.vq_n_centers = pl.vq_n;
+    qp.kmeans_n_iters = pl.n_iters; qp.pq_kmeans_type = CUVS_KMEANS_TYPE_KMEANS_BALANCED;
+    qp.max_train_points_per_pq_code = pl.max_pq; qp.max_train_points_per_vq_cluster = pl.max_vq;
+    q = pq_build(res, qp, f32_rows{train.data(), m, dim, true});
+  }
+  v.vq_book = dev_buf<__half>::persistent((size_t)v.vq_n * dim);
+  v.pq_book = dev_buf<__half>::persistent((size_t)kVpqBookN * v.pq_len);
+  vpq_round_book(res, q->vq_book.data(), (int64_t)v.vq_n * dim, v.vq_book.data(), q->vq_book.data());
+  vpq_round_book(res, q->pq_book.data(), (int64_t)kVpqBookN * v.pq_len, v.pq_book.data(), q->pq_book.data());
+  v.codes = dev_buf<uint8_t>::persistent((size_t)n * v.stride);
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t(256) << 20) / (dim * 4)));
+  dev_buf<float> f;
+  dev_buf<char> staging;  // (contiguous rows need none)
+  if (idx.dtype != elem_t::f32) f = dev_buf<float>(res, (size_t)(chunk * dim));
+  dev_buf<uint32_t> labels(res, (size_t)chunk);
+  dev_buf<uint8_t> codes(res, (size_t)chunk * pl.pq_dim);
+  for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+    const int64_t cnt = std::min(chunk, n - r0);
+    const char* src   = static_cast<const char*>(idx.data) + (size_t)r0 * dim * esz;
+    const float* x    = reinterpret_cast<const float*>(src);
+    if (idx.dtype != elem_t::f32) {
+      vpq_rows_to_float(res, src, idx.dtype, 1, cnt, dim, f.data(), staging);
+      x = f.data();
+    }
+    kmeans_predict<float>(res, x, cnt, dim, q->vq_book.data(), (int)v.vq_n, labels.data());
+    pq_encode(res, *q, x, dim, cnt, labels.data(), codes.data());
+    hipLaunchKernelGGL(vpq_pack_kernel, dim3(vpq_grid(res, cnt * (int64_t)v.stride)), dim3(256), 0, res.stream,
+                       reinterpret_cast<const uint8_t*>(labels.data()), sizeof(uint32_t), codes.data(), (size_t)pl.pq_dim, cnt, v.pq_dim,
+                       v.pq_len, v.lane_bytes, v.codes.data() + (size_t)r0 * v.stride);
+    HIP_TRY(hipGetLastError());
+  }
+  sync(res);
+  idx.owned = dev_buf<char>();
+  idx.data  = nullptr;
+}
+
 std::unique_ptr<cagra_index> cagra_build(resources& res, const cuvsCagraIndexParams& p, const void* data, elem_t et,
                                          int64_t n, int64_t dim, bool is_host)
 {
   const int metric = (int)p.metric;
   cagra_check_build(p, et);
+  vpq_plan vplan{};
+  // refusals come before any device work (host arithmetic only; cuvsCagraBuild has made the same call before it looked at
+  // its handle, the tiered index and the multi-GPU index never get here with compression parameters)
+  if (p.compression != nullptr) vplan = cagra_vpq_plan(p, n, dim);
   CUVS_EXPECTS(n > 1, "cagra: need at least two rows");
   auto idx    = std::make_unique<cagra_index>();
   idx->metric = metric;
@@ -1486,6 +1915,8 @@ std::unique_ptr<cagra_index> cagra_build(resources& res, const cuvsCagraIndexPar
   optimize_graph(res, knn.data(), n, K, degree, idx->graph.data(), res.cagra_guarantee_connectivity);
   cagra_set_norms(res, *idx);
   sync(res);
+  // the graph is made on the original rows; the index then keeps the compressed rows only (cagra_build.cuh:2301-2311)
+  if (p.compression != nullptr) cagra_compress(res, *idx, vplan);
   return idx;
 }
 
@@ -1516,6 +1947,12 @@ cagra_index& get_cagra(cuvsCagraIndex_t index)
 {
   CUVS_EXPECTS(index != nullptr && index->addr != 0, "CAGRA index is not built");
   return *reinterpret_cast<cagra_index*>(index->addr);
+}
+
+// the entry points that need the original rows (the reference refuses them for every dataset that is not strided)
+void cagra_refuse_vpq(const cagra_index& idx, const char* what)
+{
+  CUVS_EXPECTS(!idx.vpq.on(), "%s: the index holds a VPQ dataset (compressed rows only), the original rows are not kept", what);
 }
 
 // a BITSET filter is read as ceil(n_bits / 32) words: refused on the host when the tensor is not 1-D or holds fewer
@@ -1639,6 +2076,7 @@ cuvsError_t cuvsCagraIndexGetDataset(cuvsCagraIndex_t index, DLManagedTensor* da
 {
   return (cuvsError_t)translate_exceptions([=] {
     auto& idx = get_cagra(index);
+    cagra_refuse_vpq(idx, "cuvsCagraIndexGetDataset");
     fill_dl_view(dataset, const_cast<void*>(idx.data), index->dtype, idx.n, idx.dim, 2, 0);
   });
 }
@@ -1654,11 +2092,12 @@ cuvsError_t cuvsCagraBuild(cuvsResources_t res_h, cuvsCagraIndexParams_t params,
                            cuvsCagraIndex_t index)
 {
   return (cuvsError_t)translate_exceptions([=] {
-    auto& res = *as_res(res_h);
     CUVS_EXPECTS(params && dataset_tensor && index, "null argument");
-    CUVS_EXPECTS(params->compression == nullptr, "cagra: VPQ compression is outside the hot path (SURVEY 2.1 #17)");
     auto& ds = dataset_tensor->dl_tensor;
     CUVS_EXPECTS(ds.ndim == 2 && is_c_contiguous(ds), "dataset must be a row-major matrix");
+    // what a compressed build cannot serve is refused from the arguments alone, before the handle or the device is touched
+    if (params->compression != nullptr) (void)cagra_vpq_plan(*params, ds.shape[0], ds.shape[1]);
+    auto& res = *as_res(res_h);
     auto idx = cagra_build(res, *params, dl_data(ds), elem_of(ds.dtype), ds.shape[0], ds.shape[1],
                            !is_device_accessible(ds));
     delete reinterpret_cast<cagra_index*>(index->addr);
@@ -1759,9 +2198,19 @@ cuvsError_t cuvsCagraSerialize(cuvsResources_t res_h, const char* filename, cuvs
       file_writer w(filename, KIND_CAGRA);
       w.scalar<int32_t>(idx.metric); w.scalar<int32_t>((int)idx.dtype); w.scalar<int64_t>(idx.n); w.scalar<int64_t>(idx.dim);
       w.scalar<uint32_t>(idx.degree); w.scalar<uint8_t>(index->dtype.code); w.scalar<uint8_t>(index->dtype.bits);
-      w.scalar<uint8_t>(include_dataset ? 1 : 0);
+      // dataset: 0 none, 1 rows, 2 VPQ (vq_n_centers, pq_len, then the two fp16 books and the rows in the reference's layout)
+      const bool vpq = idx.vpq.on();
+      w.scalar<uint8_t>(include_dataset ? (vpq ? 2 : 1) : 0);
       w.device_array(res, idx.graph.data(), idx.graph.bytes());
-      if (include_dataset) w.device_array(res, idx.data, (size_t)idx.n * idx.dim * elem_size(idx.dtype));
+      if (include_dataset && vpq) {
+        w.scalar<uint32_t>(idx.vpq.vq_n); w.scalar<uint32_t>(idx.vpq.pq_len);
+        w.device_array(res, idx.vpq.vq_book.data(), idx.vpq.vq_book.bytes());
+        w.device_array(res, idx.vpq.pq_book.data(), idx.vpq.pq_book.bytes());
+        w.scalar<uint64_t>((uint64_t)idx.n * idx.vpq.row_len);
+        vpq_store_rows(res, idx, [&](const void* p, size_t bytes) { w.raw(p, bytes); });
+      } else if (include_dataset) {
+        w.device_array(res, idx.data, (size_t)idx.n * idx.dim * elem_size(idx.dtype));
+      }
       return;
     }
     // reference record sequence (cagra_serialize.cuh:49-75, dataset_serialize.hpp:38-60,82-87): dtype prefix,
@@ -1777,10 +2226,27 @@ cuvsError_t cuvsCagraSerialize(cuvsResources_t res_h, const char* filename, cuvs
     w.scalar<uint32_t>(idx.degree);
     w.scalar<int32_t>(idx.metric);
     w.device_array(res, 'u', 4, {idx.n, idx.degree}, idx.graph.data());
-    const bool with_data = include_dataset && idx.data != nullptr && idx.n > 0;
+    const bool with_vpq  = include_dataset && idx.vpq.on() && idx.n > 0;
+    const bool with_data = (include_dataset && idx.data != nullptr && idx.n > 0) || with_vpq;
     const bool with_src = idx.source_indices.data() != nullptr;
     w.scalar<uint32_t>((with_data ? 1u : 0u) | (with_src ? 2u : 0u));
-    if (with_data) {
+    if (with_vpq) {
+      // dataset_serialize.hpp:60-73,107-111: tag 3 (VPQ), CUDA_R_16F, n_rows (int64), dim, vq_n_centers, pq_n_centers, pq_len,
+      // encoded_row_length (uint32 each), then vq_code_book, pq_code_book and the rows [uint32 label][codes][zero padding]
+      const auto& v = idx.vpq;
+      w.scalar<uint32_t>(3u);
+      w.scalar<uint32_t>(cuda_dtype_code(elem_t::f16));
+      w.scalar<int64_t>(idx.n);
+      w.scalar<uint32_t>((uint32_t)idx.dim);
+      w.scalar<uint32_t>(v.vq_n);
+      w.scalar<uint32_t>(kVpqBookN);
+      w.scalar<uint32_t>(v.pq_len);
+      w.scalar<uint32_t>(v.row_len);
+      w.device_array(res, 'e', 2, {(int64_t)v.vq_n, idx.dim}, v.vq_book.data());
+      w.device_array(res, 'e', 2, {(int64_t)kVpqBookN, (int64_t)v.pq_len}, v.pq_book.data());
+      w.header('u', 1, {idx.n, (int64_t)v.row_len});  // the rows leave in chunks, converted to the reference's layout
+      vpq_store_rows(res, idx, [&](const void* p, size_t bytes) { w.raw(p, bytes); });
+    } else if (with_data) {
       const size_t es = elem_size(idx.dtype);
       w.scalar<uint32_t>(2u);
       w.scalar<uint32_t>(cuda_dtype_code(idx.dtype));
@@ -1807,7 +2273,21 @@ cuvsError_t cuvsCagraDeserialize(cuvsResources_t res_h, const char* filename, cu
       idx->dim = r.scalar<int64_t>(); idx->degree = r.scalar<uint32_t>();
       uint8_t code = r.scalar<uint8_t>(), bits = r.scalar<uint8_t>(), has_data = r.scalar<uint8_t>();
       idx->graph = r.device_array<uint32_t>(res);
-      if (has_data) {
+      if (has_data == 2) {
+        const uint32_t vq_n = r.scalar<uint32_t>(), pq_len = r.scalar<uint32_t>();
+        CUVS_EXPECTS(idx->dim > 0 && (pq_len == 2 || pq_len == 4) && idx->dim % pq_len == 0 && vq_n > 0,
+                     "cagra::deserialize: bad VPQ dataset header (pq_len %u, vq_n_centers %u)", pq_len, vq_n);
+        idx->vpq.set_shape(idx->dim, vq_n, pq_len);
+        idx->vpq.vq_book = r.device_array<__half>(res);
+        idx->vpq.pq_book = r.device_array<__half>(res);
+        const uint64_t row_bytes = r.scalar<uint64_t>();
+        CUVS_EXPECTS(idx->metric == M_L2Expanded, "VPQ compression is only supported with L2Expanded distance mertric");
+        CUVS_EXPECTS((int64_t)idx->vpq.vq_book.size() == (int64_t)vq_n * idx->dim && idx->vpq.pq_book.size() == (size_t)kVpqBookN * pq_len &&
+                       row_bytes == (uint64_t)idx->n * idx->vpq.row_len,
+                     "cagra::deserialize: the VPQ dataset does not match the graph");
+        vpq_load_rows(res, *idx, [&](void* p, size_t bytes) { r.raw(p, bytes); });
+        sync(res);
+      } else if (has_data) {
         idx->owned = r.device_array<char>(res);
         idx->data  = idx->owned.data();
       }
@@ -1835,8 +2315,39 @@ cuvsError_t cuvsCagraDeserialize(cuvsResources_t res_h, const char* filename, cu
         uint32_t tag = r.scalar<uint32_t>();
         if (tag == 1u) {
           (void)r.scalar<uint32_t>();  // empty dataset: suggested dim only
+        } else if (tag == 3u) {
+          // a VPQ dataset (dataset_serialize.hpp:135-160). The file is untrusted: everything the walk indexes with is checked here
+          const uint32_t code = r.scalar<uint32_t>();
+          CUVS_EXPECTS(code == cuda_dtype_code(elem_t::f16) || code == cuda_dtype_code(elem_t::f32),
+                       "cagra::deserialize: VPQ codebook element type %u is neither CUDA_R_16F nor CUDA_R_32F", code);
+          const int64_t rows    = r.scalar<int64_t>();
+          const uint32_t dim    = r.scalar<uint32_t>(), vq_n = r.scalar<uint32_t>(), pq_n = r.scalar<uint32_t>();
+          const uint32_t pq_len = r.scalar<uint32_t>(), row_len = r.scalar<uint32_t>();
+          CUVS_EXPECTS(idx->metric == M_L2Expanded, "VPQ compression is only supported with L2Expanded distance mertric");
+          CUVS_EXPECTS(pq_n == kVpqBookN, "cagra::deserialize: VPQ dataset with pq_n_centers %u (only 256, pq_bits 8, is supported)", pq_n);
+          CUVS_EXPECTS(pq_len == 2 || pq_len == 4, "cagra::deserialize: VPQ dataset with pq_len %u (only 2 and 4 are supported)", pq_len);
+          CUVS_EXPECTS(dim > 0 && dim % pq_len == 0, "cagra::deserialize: VPQ dataset dim %u is not a multiple of pq_len %u", dim, pq_len);
+          CUVS_EXPECTS(rows == idx->n && (int64_t)dim == idx->dim && vq_n > 0, "cagra::deserialize: dataset shape does not match the graph");
+          idx->vpq.set_shape(idx->dim, vq_n, pq_len);
+          CUVS_EXPECTS(row_len == idx->vpq.row_len, "cagra::deserialize: VPQ dataset with encoded_row_length %u, expected %u", row_len,
+                       idx->vpq.row_len);
+          auto read_book = [&](int64_t count) {
+            if (code == cuda_dtype_code(elem_t::f16)) return r.device_array<__half>(res, count);
+            dev_buf<float> b = r.device_array<float>(res, count);  // fp32 codebooks (vpq_dataset<float>) are rounded to fp16
+            auto out = dev_buf<__half>::persistent((size_t)count);
+            vpq_round_book(res, b.data(), count, out.data(), nullptr);
+            sync(res);
+            return out;
+          };
+          idx->vpq.vq_book = read_book((int64_t)vq_n * dim);
+          idx->vpq.pq_book = read_book((int64_t)kVpqBookN * pq_len);
+          const npy_header eh = r.header();
+          CUVS_EXPECTS(eh.itemsize == 1 && !eh.fortran && eh.count() == rows * (int64_t)row_len,
+                       "cagra::deserialize: the encoded rows of the VPQ dataset are not %ld x %u bytes", (long)rows, row_len);
+          vpq_load_rows(res, *idx, [&](void* p, size_t bytes) { r.raw(p, bytes); });
+          sync(res);
         } else {
-          CUVS_EXPECTS(tag == 2u, "Failed to deserialize dataset: instance tag %u (VPQ-compressed datasets are not built)", tag);
+          CUVS_EXPECTS(tag == 2u, "Failed to deserialize dataset: unknown instance tag %u", tag);
           uint32_t code = r.scalar<uint32_t>();
           CUVS_EXPECTS(code == cuda_dtype_code(idx->dtype), "cagra::deserialize: dataset element type %u does not match the index dtype", code);
           int64_t rows = r.scalar<int64_t>();
@@ -1869,6 +2380,7 @@ cuvsError_t cuvsCagraSerializeToHnswlib(cuvsResources_t res_h, const char* filen
   return (cuvsError_t)translate_exceptions([=] {
     auto& res = *as_res(res_h);
     auto& idx = get_cagra(index);
+    cagra_refuse_vpq(idx, "cuvsCagraSerializeToHnswlib");
     CUVS_EXPECTS(idx.data != nullptr && idx.n > 0, "Invalid CAGRA dataset of size 0 during serialization");
     CUVS_EXPECTS(idx.metric != M_BitwiseHamming, "cagra::serialize_to_hnswlib: hnswlib has no BitwiseHamming space; a Hamming "
                                                  "index cannot be exported");
@@ -1924,6 +2436,7 @@ cuvsError_t cuvsCagraExtend(cuvsResources_t res_h, cuvsCagraExtendParams_t param
   return (cuvsError_t)translate_exceptions([=] {
     auto& res = *as_res(res_h);
     auto& idx = get_cagra(index);
+    cagra_refuse_vpq(idx, "cuvsCagraExtend");
     CUVS_EXPECTS(additional_dataset != nullptr, "additional_dataset is null");
     auto& t = additional_dataset->dl_tensor;
     CUVS_EXPECTS(t.ndim == 2 && is_c_contiguous(t) && t.shape[1] == idx.dim, "additional_dataset must be [m, dim] row-major");
@@ -1956,6 +2469,8 @@ cuvsError_t cuvsCagraMerge(cuvsResources_t res_h, cuvsCagraIndexParams_t params,
     // a BITSET over the concatenated rows keeps the rows whose bit is set (cagra_merge.cuh:94-131: the merged index is built on
     // the kept rows, in order); bitmaps are refused as in the reference (:45-46)
     CUVS_EXPECTS(filter.type == NO_FILTER || filter.type == BITSET, "Bitmap filter isn't supported inside cagra::merge");
+    // the reference's merge builds over an uncompressed dataset only (cagra_merge.cuh); compress the merged rows with a build
+    CUVS_EXPECTS(params->compression == nullptr, "cuvsCagraMerge: VPQ compression parameters are not supported");
     const uint32_t* bits = nullptr;
     if (filter.type == BITSET) {
       CUVS_EXPECTS(filter.addr != 0, "cagra::merge: the filter has no tensor");
@@ -1967,6 +2482,7 @@ cuvsError_t cuvsCagraMerge(cuvsResources_t res_h, cuvsCagraIndexParams_t params,
     int64_t total = 0;
     for (size_t i = 0; i < num_indices; ++i) {
       auto& ix = get_cagra(indices[i]);
+      cagra_refuse_vpq(ix, "cuvsCagraMerge");
       CUVS_EXPECTS(ix.data != nullptr, "cagra::merge: index %zu has no dataset", i);
       // the merged index numbers its rows by position in the concatenation, and the BITSET is over those positions: an input
       // that reports source ids would be renumbered silently, so it is refused
@@ -2042,6 +2558,44 @@ extern "C" __attribute__((visibility("default"))) cuvsError_t cuvsAmdCagraWorkCo
 extern "C" __attribute__((visibility("default"))) cuvsError_t cuvsAmdCagraSetGuaranteeConnectivity(cuvsResources_t res_h, int on)
 {
   return (cuvsError_t)translate_exceptions([=] { cuvs_amd::as_res(res_h)->cagra_guarantee_connectivity = on != 0; });
+}
+
+// The VPQ dataset of a compressed index (include/cuvs_amd/extensions.h; the reference reads it through the C++ index only).
+extern "C" __attribute__((visibility("default"))) cuvsError_t cuvsAmdCagraIndexGetVpqInfo(cuvsCagraIndex_t index, uint32_t out[5])
+{
+  return (cuvsError_t)translate_exceptions([=] {
+    auto& idx = get_cagra(index);
+    CUVS_EXPECTS(idx.vpq.on(), "cuvsAmdCagraIndexGetVpqInfo: the index holds no VPQ dataset");
+    CUVS_EXPECTS(out != nullptr, "null argument");
+    out[0] = idx.vpq.vq_n; out[1] = cuvs_amd::kVpqBookN; out[2] = idx.vpq.pq_len; out[3] = idx.vpq.row_len; out[4] = (uint32_t)idx.dim;
+  });
+}
+
+extern "C" __attribute__((visibility("default"))) cuvsError_t cuvsAmdCagraIndexGetVpq(cuvsResources_t res_h, cuvsCagraIndex_t index,
+                                                                                      DLManagedTensor* vq_book, DLManagedTensor* pq_book,
+                                                                                      DLManagedTensor* codes)
+{
+  return (cuvsError_t)translate_exceptions([=] {
+    using namespace cuvs_amd;
+    auto& res = *as_res(res_h);
+    auto& idx = get_cagra(index);
+    CUVS_EXPECTS(idx.vpq.on(), "cuvsAmdCagraIndexGetVpq: the index holds no VPQ dataset");
+    CUVS_EXPECTS(vq_book && pq_book && codes, "null argument");
+    const auto& v = idx.vpq;
+    auto check = [](const DLTensor& t, uint8_t code, uint8_t bits, int64_t rows, int64_t cols, const char* what) {
+      CUVS_EXPECTS(is_device_accessible(t) && dtype_is(t.dtype, code, bits) && t.ndim == 2 && is_c_contiguous(t) && t.shape[0] == rows &&
+                     t.shape[1] == cols,
+                   "cuvsAmdCagraIndexGetVpq: %s must be a device %s [%ld, %ld] row-major matrix", what, bits == 16 ? "float16" : "uint8",
+                   (long)rows, (long)cols);
+    };
+    check(vq_book->dl_tensor, kDLFloat, 16, v.vq_n, idx.dim, "vq_book");
+    check(pq_book->dl_tensor, kDLFloat, 16, kVpqBookN, v.pq_len, "pq_book");
+    check(codes->dl_tensor, kDLUInt, 8, idx.n, v.row_len, "codes");
+    copy_async(res, dl_data(vq_book->dl_tensor), v.vq_book.data(), v.vq_book.bytes());
+    copy_async(res, dl_data(pq_book->dl_tensor), v.pq_book.data(), v.pq_book.bytes());
+    vpq_export_rows(res, idx, 0, idx.n, static_cast<uint8_t*>(dl_data(codes->dl_tensor)));
+    sync(res);
+  });
 }
 
 // cagra::helpers::optimize (cpp/include/cuvs/neighbors/cagra_optimize.hpp; graph_core.cuh:1706-1809): kNN graph

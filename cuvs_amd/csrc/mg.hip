@@ -302,6 +302,10 @@ std::unique_ptr<mg_index> mg_build(cuvsResources_t res_h, const algo_ops& ops, i
   auto& ds = dataset->dl_tensor;
   check_matrix(ds, "dataset");
   CUVS_EXPECTS(mode == CUVS_NEIGHBORS_MG_REPLICATED || mode == CUVS_NEIGHBORS_MG_SHARDED, "unknown distribution mode %d", mode);
+  // a shard with compressed rows could be neither extended nor re-distributed: refused before any shard is made
+  if (&ops == &kCagraOps)
+    CUVS_EXPECTS(static_cast<cuvsCagraIndexParams_t>(base_params)->compression == nullptr,
+                 "cuvsMultiGpuCagraBuild: VPQ compression parameters are not supported by the multi-GPU index");
   auto idx  = std::make_unique<mg_index>();
   idx->ops  = &ops;
   idx->mode = mode;

@@ -26,9 +26,9 @@
 #include "common.hpp"
 #include "device_utils.hpp"
 #include "ops.hpp"
+#include "pq_quantize.hpp"
 
 #include <cuvs/cluster/kmeans.h>
-#include <cuvs/preprocessing/quantize/pq.h>
 #include <cuvs_amd/extensions.h>
 
 #include <algorithm>
@@ -41,17 +41,6 @@ namespace cuvs_amd {
 namespace {
 
 const DLDataType kPqF32{kDLFloat, 32, 1};
-
-struct product_quantizer {
-  cuvsProductQuantizerParams p{};  // filled: pq_dim and vq_n_centers are the values in use
-  int64_t dim     = 0;
-  int64_t pq_len  = 0;
-  int64_t book_n  = 0;             // 2^pq_bits
-  int64_t vq_n    = 0;             // 0: no VQ
-  dev_buf<float> pq_book;          // [pq_dim * book_n, pq_len] (use_subspaces) or [book_n, pq_len]
-  dev_buf<float> vq_book;          // [vq_n, dim]
-  int64_t code_bytes() const { return ((int64_t)p.pq_dim * p.pq_bits + 7) / 8; }
-};
 
 std::atomic<unsigned long long> g_encode_launches[3];  // default (any R), plain, default with R > 1 rows per lane
 
@@ -250,6 +239,8 @@ void pq_launch_default(resources& res, const encode_args& a)
   }
 }
 
+}  // namespace
+
 void pq_encode(resources& res, const product_quantizer& q, const float* x, int64_t ld, int64_t n, const uint32_t* labels,
                uint8_t* codes)
 {
@@ -284,6 +275,8 @@ void pq_encode(resources& res, const product_quantizer& q, const float* x, int64
   }
   HIP_TRY(hipGetLastError());
 }
+
+namespace {
 
 // ---------------------------------------------------------------- decoder
 // a lane writes V consecutive columns of one subspace: rows leave as coalesced 4 V-byte stores; the book is read through the
@@ -391,11 +384,6 @@ void pq_train_book(resources& res, const product_quantizer& q, const float* x, i
   CUVS_EXPECTS(e == CUVS_SUCCESS, "%s", last_error_text().c_str());
 }
 
-struct f32_rows {
-  const float* data;
-  int64_t n, dim;
-  bool device;
-};
 f32_rows pq_dataset_view(DLManagedTensor* t)
 {
   CUVS_EXPECTS(t != nullptr, "null argument");
@@ -414,6 +402,8 @@ void pq_check_params(const cuvsProductQuantizerParams& p)
   CUVS_EXPECTS(p.pq_kmeans_type == CUVS_KMEANS_TYPE_KMEANS || p.pq_kmeans_type == CUVS_KMEANS_TYPE_KMEANS_BALANCED,
                "unknown pq_kmeans_type %d", (int)p.pq_kmeans_type);
 }
+
+}  // namespace
 
 std::unique_ptr<product_quantizer> pq_build(resources& res, const cuvsProductQuantizerParams& params, const f32_rows& ds)
 {
@@ -473,6 +463,8 @@ std::unique_ptr<product_quantizer> pq_build(resources& res, const cuvsProductQua
   sync(res);
   return q;
 }
+
+namespace {
 
 product_quantizer& get_pq(cuvsProductQuantizer_t q)
 {

@@ -22,6 +22,17 @@ class _CIndexParams(C.Structure):
     ]
 
 
+class _CCompressionParams(C.Structure):
+    _fields_ = [
+        ("pq_bits", C.c_uint32),
+        ("pq_dim", C.c_uint32),
+        ("vq_n_centers", C.c_uint32),
+        ("kmeans_n_iters", C.c_uint32),
+        ("vq_kmeans_trainset_fraction", C.c_double),
+        ("pq_kmeans_trainset_fraction", C.c_double),
+    ]
+
+
 class _CSearchParams(C.Structure):
     _fields_ = [
         ("max_queries", C.c_size_t),
@@ -50,9 +61,40 @@ class _CIndex(C.Structure):
 _BUILD_ALGOS = {"auto": 0, "ivf_pq": 1, "nn_descent": 2, "iterative_cagra_search": 3}
 
 
+class CompressionParams:
+    """cuvsCagraCompressionParams (reference: cagra.pyx CompressionParams): VPQ compression of the dataset of a CAGRA index.
+    Zero fields are filled at build time: pq_dim = ceil(dim / 4), vq_n_centers = sqrt(n) rounded up to 8, the trainset
+    fractions by the reference's heuristics. Served: pq_bits 8 and dim / pq_dim of 2 or 4, sqeuclidean only."""
+
+    def __init__(self, *, pq_bits=8, pq_dim=0, vq_n_centers=0, kmeans_n_iters=25, vq_kmeans_trainset_fraction=0.0,
+                 pq_kmeans_trainset_fraction=0.0):
+        self._p = C.POINTER(_CCompressionParams)()
+        check(lib().cuvsCagraCompressionParamsCreate(C.byref(self._p)))
+        p = self._p.contents
+        p.pq_bits = pq_bits
+        p.pq_dim = pq_dim
+        p.vq_n_centers = vq_n_centers
+        p.kmeans_n_iters = kmeans_n_iters
+        p.vq_kmeans_trainset_fraction = vq_kmeans_trainset_fraction
+        p.pq_kmeans_trainset_fraction = pq_kmeans_trainset_fraction
+
+    pq_bits = property(lambda self: self._p.contents.pq_bits)
+    pq_dim = property(lambda self: self._p.contents.pq_dim)
+    vq_n_centers = property(lambda self: self._p.contents.vq_n_centers)
+    kmeans_n_iters = property(lambda self: self._p.contents.kmeans_n_iters)
+    vq_kmeans_trainset_fraction = property(lambda self: self._p.contents.vq_kmeans_trainset_fraction)
+    pq_kmeans_trainset_fraction = property(lambda self: self._p.contents.pq_kmeans_trainset_fraction)
+
+    def __del__(self):
+        try:
+            lib().cuvsCagraCompressionParamsDestroy(self._p)
+        except Exception:
+            pass
+
+
 class IndexParams:
     def __init__(self, *, metric="sqeuclidean", intermediate_graph_degree=128, graph_degree=64, build_algo="ivf_pq",
-                 nn_descent_niter=20, guarantee_connectivity=False):
+                 nn_descent_niter=20, guarantee_connectivity=False, compression=None):
         # guarantee_connectivity: cagra::index_params::guarantee_connectivity (cagra.hpp:193; C++-only in the reference,
         # here a switch on the handle: cuvsAmdCagraSetGuaranteeConnectivity)
         self.guarantee_connectivity = bool(guarantee_connectivity)
@@ -65,6 +107,10 @@ class IndexParams:
         p.nn_descent_niter = nn_descent_niter
         self._algo = _BUILD_ALGOS[build_algo]
         self.metric = metric
+        # the C struct holds a pointer into the CompressionParams object: keep it alive as long as these parameters
+        self.compression = compression
+        if compression is not None:
+            p.compression = C.cast(compression._p, C.c_void_p)
 
     def _c_build_algo(self):
         # "auto" builds with IVF-PQ as in the reference's Python layer (cagra.pyx), except for bitwise_hamming, which IVF-PQ
@@ -138,6 +184,29 @@ class Index:
         check(lib().cuvsCagraIndexGetGraph(self._p, C.byref(m)))
         return view_to_torch(m, "cuda")
 
+    def _vpq_info(self):
+        out = (C.c_uint32 * 5)()
+        return list(out) if lib().cuvsAmdCagraIndexGetVpqInfo(self._p, out) == 1 else None
+
+    @property
+    def compressed(self):
+        """True when the index holds a VPQ dataset (built with IndexParams(compression=...) or loaded from such a file)"""
+        return self.trained and self._vpq_info() is not None
+
+    @auto_sync_resources
+    def vpq(self, resources=None):
+        """(vq_book fp16 [vq_n_centers, dim], pq_book fp16 [256, pq_len], codes uint8 [n, row_len]) of a compressed index, on
+        the device; a row of codes is [uint32 VQ label][pq_dim code bytes][zero padding to 4 bytes] (the reference's layout)."""
+        out = (C.c_uint32 * 5)()
+        check(lib().cuvsAmdCagraIndexGetVpqInfo(self._p, out))
+        vq_n, pq_n, pq_len, row_len, dim = list(out)
+        vq = torch.empty((vq_n, dim), dtype=torch.float16, device="cuda")
+        pq = torch.empty((pq_n, pq_len), dtype=torch.float16, device="cuda")
+        codes = torch.empty((len(self), row_len), dtype=torch.uint8, device="cuda")
+        tv, tp, tc = Tensor(vq), Tensor(pq), Tensor(codes)
+        check(lib().cuvsAmdCagraIndexGetVpq(resources.get_c_obj(), self._p, tv.ptr, tp.ptr, tc.ptr))
+        return vq, pq, codes
+
 
 @auto_sync_resources
 def build(index_params, dataset, resources=None):
@@ -151,7 +220,7 @@ def build(index_params, dataset, resources=None):
     finally:
         lib().cuvsAmdCagraSetGuaranteeConnectivity(resources.get_c_obj(), C.c_int(0))
     index_params._p.contents.build_algo = 1  # keep Destroy's graph_build_params bookkeeping valid
-    idx._keep = ds  # the index views a device dataset
+    idx._keep = None if index_params.compression is not None else ds  # the index views a device dataset unless it compressed it
     idx.trained = True
     return idx
 

@@ -53,6 +53,15 @@ CUVS_EXPORT cuvsError_t cuvsAmdCagraOptimize(cuvsResources_t res, DLManagedTenso
 CUVS_EXPORT cuvsError_t cuvsAmdCagraBuildKnnGraph(cuvsResources_t res, cuvsCagraIndexParams_t params, DLManagedTensor* dataset,
                                                   DLManagedTensor* knn_graph);
 
+/* The VPQ dataset of a CAGRA index built with cuvsCagraIndexParams::compression or loaded from a file that holds one (the
+ * reference exposes it through its C++ index only). cuvsAmdCagraIndexGetVpqInfo: out = {vq_n_centers,
+ * pq_n_centers, pq_len, encoded row length in bytes, dim}; an error for an index that is not compressed.
+ * cuvsAmdCagraIndexGetVpq fills caller-allocated device tensors: vq_book fp16 [vq_n_centers, dim], pq_book fp16 [256, pq_len],
+ * codes uint8 [n, row length] in the reference's row layout: [uint32 VQ label][pq_dim code bytes][zero padding to 4 bytes]. */
+CUVS_EXPORT cuvsError_t cuvsAmdCagraIndexGetVpqInfo(cuvsCagraIndex_t index, uint32_t out[5]);
+CUVS_EXPORT cuvsError_t cuvsAmdCagraIndexGetVpq(cuvsResources_t res, cuvsCagraIndex_t index, DLManagedTensor* vq_book,
+                                                DLManagedTensor* pq_book, DLManagedTensor* codes);
+
 /* index.codes_layout() of the reference's C++ index (cpp/include/cuvs/neighbors/ivf_pq.hpp:40-90; the C ABI sets the layout in
  * cuvsIvfPqIndexParams but has no getter): 0 = CUVS_IVF_PQ_LIST_LAYOUT_FLAT, 1 = CUVS_IVF_PQ_LIST_LAYOUT_INTERLEAVED. */
 CUVS_EXPORT cuvsError_t cuvsAmdIvfPqIndexGetCodesLayout(cuvsIvfPqIndex_t index, int* layout);
