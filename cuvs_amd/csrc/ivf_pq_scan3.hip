@@ -38,8 +38,10 @@
 #include <cfloat>
 #include <cmath>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <type_traits>
+#include <utility>
 
 namespace cuvs_amd {
 
@@ -2030,9 +2032,11 @@ __global__ __launch_bounds__(256) void flat_rescore_kernel(const rescore_params 
 // ------------------------------------------------------------------ single-query list scan (head phase, handed-back pairs)
 // One (query, list) pair per work item with no bound to prune against: the LUT scan kernel of ivf_pq_search.hip spends
 // such an item on top-list bookkeeping (16 wave lists with serial insertions while the bounds are cold, then their
-// merge: ~130 k cycles for 6 k rows). Here the workgroup builds the query's LUT, writes the score KEY of every row of
-// the list to LDS and selects the k smallest by (score, row) with three histogram passes - select_k's scheme
-// (select_k.hip) on data that never leaves the LDS. Scores are the reference's (same entries, same summation order).
+// merge: ~130 k cycles for 6 k rows). Here the workgroup builds the query's LUT, scores every row of the list and selects
+// the k smallest by (score, row): a threshold from the minima of small groups of threads, the keys at or below it ranked in
+// the LDS. The score keys themselves stay out of the LDS (a thread keeps its smallest, that key's row and its second
+// smallest; the rows of the few threads with several keys at or below the threshold are scored once more), so a workgroup
+// needs its LUT + 12 KiB and three of them share a CU. Scores are the reference's (same entries, same summation order).
 struct head_params {
   const work_item* items;
   const uint32_t* item_begin;  // device scalars (item_begin == nullptr: from 0)
@@ -2063,8 +2067,26 @@ struct head_params {
 // candidates of a list chunk at or below its threshold (about k of them) + the kept ones (up to k)
 static inline int head_cand(int k) { return k <= 128 ? 512 : 1024; }
 
-template <int LUT, bool ACC_HALF, int NT>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void pq_head_kernel(const head_params a)
+// rows of a list chunk per thread; groups of four code chunks (64 subspaces) the fp16-LUT variants unroll (pq_dim up to 128)
+constexpr int kHeadRowsPerThread = 16;
+constexpr int kHeadGroups16      = 2;
+
+// (byte B of w) << 1, the byte offset of an fp16 LUT entry within its subspace, in one instruction (left to the compiler:
+// a byte extract and a shift-add of the LDS base)
+template <int B>
+__device__ __forceinline__ uint32_t code_byte_x2(uint32_t w)
+{
+  uint32_t r;
+  if constexpr (B == 0) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(r) : "s"(1u), "v"(w));
+  if constexpr (B == 1) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "=v"(r) : "s"(1u), "v"(w));
+  if constexpr (B == 2) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "=v"(r) : "s"(1u), "v"(w));
+  if constexpr (B == 3) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3" : "=v"(r) : "s"(1u), "v"(w));
+  return r;
+}
+
+// WPE: waves per SIMD the kernel is compiled for (4: 128 registers, 6: 80 - three 512-thread workgroups per CU)
+template <int LUT, bool ACC_HALF, int NT, int WPE>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void pq_head_kernel(const head_params a)
 {
   constexpr bool LUT32 = LUT == 0 || (LUT == 2 && !ACC_HALF);
   using lut_t = std::conditional_t<LUT32, float, _Float16>;
@@ -2074,13 +2096,16 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
   float* cv       = rv + 256;                                                            // [256] list centre
   unsigned long long* min64 = reinterpret_cast<unsigned long long*>(cv + 256);           // [2]
   int* ctrl       = reinterpret_cast<int*>(min64 + 2);                           // [8]
-  // (no static LDS in this kernel: the LUT sits at LDS address 0 and a lookup's address is (code byte) << 1 - one SDWA shift)
+  // (no static LDS in this kernel: the LUT sits at LDS address 0 and a lookup's address is (code byte) << 1 - one SDWA shift;
+  // subspace s adds s * 512 bytes, which the fp16-LUT variants carry in the read's immediate offset)
   work_item& cur  = *reinterpret_cast<work_item*>(ctrl + 8);                     // the current item, 16 bytes
-  uint32_t* tk    = reinterpret_cast<uint32_t*>(ctrl + 12);                      // [NT] smallest key of every thread
+  uint32_t* tk    = reinterpret_cast<uint32_t*>(ctrl + 12);                      // [NT] smallest key of every thread's group; then the
+                                                                                 // threads with more than one key at or below the threshold
   const int kHCand = a.hcand;
   uint2* cand     = reinterpret_cast<uint2*>(tk + NT);                           // [2][kHCand] candidates (key, row), two buffers: 16-byte aligned -
                                                                                  // the rank pass reads two entries per ds_read_b128
-  uint32_t* keys  = reinterpret_cast<uint32_t*>(cand + 2 * kHCand);              // [cap_rows] score keys of the current chunk
+  // (the score keys are not stored: a thread keeps its smallest key, that key's row and its second smallest key in
+  // registers - 44 KiB of LDS instead of 80 with a 32 KiB LUT, three workgroups per CU)
   static_assert(sizeof(work_item) == 16, "work_item");
 
   const int tid = threadIdx.x;
@@ -2090,6 +2115,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
   const uint32_t share0 = min(n_items, xcd * chunk), share_len = min(chunk, n_items - share0);
   const work_item* share = a.items + item0 + share0;
   const uint4* codes16   = reinterpret_cast<const uint4*>(a.codes);
+  // 1.0f the compiler cannot see through: fma((float)e, one, acc) stays an fma (v_fma_mix_f32 takes the fp16 entry as it is)
+  float one = 1.0f;
+  asm("" : "+s"(one));
 
   for (uint32_t round = 0;; ++round) {
     __syncthreads();
@@ -2198,57 +2226,92 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     phase(1);
     const int k = (int)a.k;
     int buf = 0;  // candidate buffer holding the kept candidates
+    // score key of row v of the list (filtered rows: invalid)
+    auto key_of = [&](uint32_t v) __attribute__((always_inline)) -> uint32_t {
+      const uint32_t fr = base_row + v;
+      const uint4* cp   = codes16 + ((size_t)(fr >> 6) * a.n_chunks) * 64 + (fr & 63u);
+      float af    = 0.f;
+      _Float16 ah = (_Float16)0.f;
+      // four chunk loads in flight; the chunk's 16 lookups are issued together, the sum follows in order (left to the
+      // compiler every lookup was followed by a wait for it: one LDS latency per entry and wave)
+      auto group = [&](int c0c) __attribute__((always_inline)) {
+        uint4 cw[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) cw[c] = cp[(size_t)min(c0c + c, (int)a.n_chunks - 1) * 64];
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc) {
+          const int c = c0c + cc;
+          if (c >= (int)a.n_chunks) break;
+          const uint32_t ws[4] = {cw[cc].x, cw[cc].y, cw[cc].z, cw[cc].w};
+          lut_t e[16];
+          if constexpr (LUT32) {
+#pragma unroll
+            for (int b = 0; b < 16; ++b) e[b] = lut[((c * 16 + b) << 8) + ((ws[b >> 2] >> ((b & 3) * 8)) & 0xffu)];
+          } else {
+            // (absolute LDS addresses - the LUT sits at address 0, pq3_head_scan checks that the kernel has no static LDS: added
+            // to the symbol of the dynamic LDS, which the compiler resolves late, every address keeps an add of 0)
+            using lds_entry = const __attribute__((address_space(3))) lut_t*;
+            auto look = [&](auto bt) __attribute__((always_inline)) {
+              constexpr int b = decltype(bt)::value;
+              e[b] = *(lds_entry)(uint32_t)((uint32_t)(c * 16 + b) * 512u + code_byte_x2<(b & 3)>(ws[b >> 2]));
+            };
+            using std::integral_constant;
+            look(integral_constant<int, 0>{}); look(integral_constant<int, 1>{}); look(integral_constant<int, 2>{}); look(integral_constant<int, 3>{});
+            look(integral_constant<int, 4>{}); look(integral_constant<int, 5>{}); look(integral_constant<int, 6>{}); look(integral_constant<int, 7>{});
+            look(integral_constant<int, 8>{}); look(integral_constant<int, 9>{}); look(integral_constant<int, 10>{}); look(integral_constant<int, 11>{});
+            look(integral_constant<int, 12>{}); look(integral_constant<int, 13>{}); look(integral_constant<int, 14>{}); look(integral_constant<int, 15>{});
+          }
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int b = 0; b < 16; ++b) {
+            if constexpr (LUT32) af += e[b];
+            else if constexpr (ACC_HALF) ah += e[b];
+            else af = __builtin_fmaf((float)e[b], one, af);  // one mixed-precision fma: rounds once, like (float)e + af
+          }
+        }
+      };
+      if constexpr (LUT32) {
+        for (int c0c = 0; c0c < (int)a.n_chunks; c0c += 4) group(c0c);
+      } else {
+        // fp16 entries: the groups of four chunks unrolled - a lookup's subspace is a constant, so its address is one shift
+        // of the code byte and the subspace's base travels in the read's immediate offset (not in an add per lookup)
+#pragma unroll
+        for (int g = 0; g < kHeadGroups16; ++g) {
+          if (g * 4 >= (int)a.n_chunks) break;
+          group(g * 4);
+        }
+        for (int c0c = 4 * kHeadGroups16; c0c < (int)a.n_chunks; c0c += 4) group(c0c);
+      }
+      const float score = ACC_HALF ? (float)ah : af;
+      bool keep = true;
+      if (a.filter_bits != nullptr) {
+        const int64_t sid = a.indices[fr];
+        keep = ((a.filter_bits[sid >> 5] >> (sid & 31)) & 1u) != 0u;
+      }
+      return keep ? float_to_key(score) : 0xffffffffu;  // (a NaN score has a key beyond every finite one as well)
+    };
     // ---- the list in chunks of cap_rows rows (one chunk for all but very long lists)
     for (uint32_t c0 = 0; c0 < len; c0 += a.cap_rows) {
       const uint32_t clen = min(a.cap_rows, len - c0);
-      // score keys of the chunk's rows (filtered rows: invalid)
-      uint32_t my_min = 0xffffffffu;
+      const uint32_t kpt  = (clen + NT - 1) / NT;  // rows of a thread (row tid + j * NT of the chunk), at most kHeadRowsPerThread
+      // score keys of the chunk's rows: every thread keeps its smallest key, that key's row and its second smallest key
+      uint32_t my_min = 0xffffffffu, my_row = 0u, my_2nd = 0xffffffffu;
+#pragma unroll 1
       for (uint32_t v = tid; v < clen; v += NT) {
-        const uint32_t fr = base_row + c0 + v;
-        const uint4* cp   = codes16 + ((size_t)(fr >> 6) * a.n_chunks) * 64 + (fr & 63u);
-        float af    = 0.f;
-        _Float16 ah = (_Float16)0.f;
-        for (int c0c = 0; c0c < (int)a.n_chunks; c0c += 4) {  // four chunk loads in flight
-          uint4 cw[4];
-#pragma unroll
-          for (int c = 0; c < 4; ++c) cw[c] = cp[(size_t)min(c0c + c, (int)a.n_chunks - 1) * 64];
-#pragma unroll
-          for (int cc = 0; cc < 4; ++cc) {
-            const int c = c0c + cc;
-            if (c >= (int)a.n_chunks) break;
-            const uint32_t ws[4] = {cw[cc].x, cw[cc].y, cw[cc].z, cw[cc].w};
-            // the chunk's 16 lookups are issued together, the sum follows in order (left to the compiler every lookup was
-            // followed by a wait for it: one LDS latency per entry and wave)
-            lut_t e[16];
-#pragma unroll
-            for (int b = 0; b < 16; ++b) e[b] = lut[((c * 16 + b) << 8) + ((ws[b >> 2] >> ((b & 3) * 8)) & 0xffu)];
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int b = 0; b < 16; ++b) {
-              if constexpr (LUT32) af += e[b];
-              else if constexpr (ACC_HALF) ah += e[b];
-              else af += (float)e[b];
-            }
-          }
-        }
-        const float score = ACC_HALF ? (float)ah : af;
-        bool keep = true;
-        if (a.filter_bits != nullptr) {
-          const int64_t sid = a.indices[fr];
-          keep = ((a.filter_bits[sid >> 5] >> (sid & 31)) & 1u) != 0u;
-        }
-        const uint32_t key = keep ? float_to_key(score) : 0xffffffffu;  // (a NaN score has a key beyond every finite one as well)
-        keys[v] = key;
-        my_min  = min(my_min, key);
+        const uint32_t key = key_of(c0 + v);
+        my_2nd = min(my_2nd, max(my_min, key));
+        my_row = key < my_min ? v : my_row;
+        my_min = min(my_min, key);
       }
       // minima of groups of four threads (k <= 64), of two (k <= 128) or of one (k <= 256: at least 2 k groups keep the
       // threshold tight) by DPP: each group is a set of rows of its own
       const int gshift = k > 128 ? 0 : (k > 64 ? 1 : 2);
+      uint32_t gmin = my_min;
       if (gshift >= 1)
-        my_min = min(my_min, (uint32_t)__builtin_amdgcn_update_dpp((int)my_min, (int)my_min, 0xb1, 0xf, 0xf, false));  // quad_perm [1,0,3,2]
+        gmin = min(gmin, (uint32_t)__builtin_amdgcn_update_dpp((int)gmin, (int)gmin, 0xb1, 0xf, 0xf, false));  // quad_perm [1,0,3,2]
       if (gshift == 2)
-        my_min = min(my_min, (uint32_t)__builtin_amdgcn_update_dpp((int)my_min, (int)my_min, 0x4e, 0xf, 0xf, false));  // quad_perm [2,3,0,1]
-      if ((tid & ((1 << gshift) - 1)) == 0) tk[tid >> gshift] = my_min;
+        gmin = min(gmin, (uint32_t)__builtin_amdgcn_update_dpp((int)gmin, (int)gmin, 0x4e, 0xf, 0xf, false));  // quad_perm [2,3,0,1]
+      if ((tid & ((1 << gshift) - 1)) == 0) tk[tid >> gshift] = gmin;
       __syncthreads();
       phase(2);
       // ---- candidates of the chunk. The scores of a list share their leading bits: a histogram select serializes on a
@@ -2271,40 +2334,61 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
           r += (o.w < mine || (o.w == mine && 4 * j + 3 < tid)) ? 1 : 0;
         }
         if (r == k_c - 1) ctrl[1] = (int)mine;
-        if (tid == 0) ctrl[2] = kept;  // append position
+        if (tid == 0) { ctrl[2] = kept; ctrl[3] = 0; }  // append position; threads with several keys at or below the threshold
       }
       __syncthreads();
       const uint32_t tau = (uint32_t)ctrl[1];
       uint2* bc = cand + buf * kHCand;
-      for (uint32_t i = tid; i < clen; i += NT) {
-        const uint32_t key = keys[i];
+      auto offer = [&](uint32_t key, uint32_t v) __attribute__((always_inline)) {
         if (key <= tau && key != 0xffffffffu) {
           const int pos = atomicAdd(&ctrl[2], 1);
-          if (pos < kHCand) bc[pos] = make_uint2(key, c0 + i);
+          if (pos < kHCand) bc[pos] = make_uint2(key, c0 + v);
         }
+      };
+      // a thread whose second smallest key is above the threshold offers its smallest; the few others (two of the ~k keys
+      // at or below the threshold in one thread's rows) are listed, and their rows are scored once more, one row per lane
+      const bool several = my_2nd <= tau && my_2nd != 0xffffffffu;
+      if (several) tk[atomicAdd(&ctrl[3], 1)] = (uint32_t)tid;  // (tk's minima were read before the barrier above)
+      else offer(my_min, my_row);
+      __syncthreads();
+      const uint32_t n_again = (uint32_t)ctrl[3] * kpt;
+      // (the two rare scoring sites below start from a copy of tid the compiler cannot see through: nothing of theirs is
+      // hoisted to the kernel's top and kept in registers through the LUT build - the fp32-LUT variants sit at 128 registers)
+      uint32_t lane = (uint32_t)tid;
+      asm volatile("" : "+v"(lane));
+#pragma unroll 1
+      for (uint32_t w = lane; w < n_again; w += NT) {
+        const uint32_t v = tk[w / kpt] + (w % kpt) * NT;
+        if (v < clen) offer(key_of(c0 + v), v);
       }
       __syncthreads();
       int cnt = ctrl[2];
       if (cnt > kHCand) {
-        // masses of equal scores at the threshold: the chunk's k smallest (key, row) one after the other instead
-        unsigned long long last = 0ull;
-        bool first = true;
+        // masses of equal scores at the threshold: the chunk's k smallest (key, row) one after the other instead. Every
+        // thread offers its smallest pair not yet taken; the thread whose pair was taken gets its next one from a new
+        // scoring of its rows, one row per lane.
+        unsigned long long best = my_min != 0xffffffffu ? ((unsigned long long)my_min << 32) | (unsigned long long)(c0 + my_row) : ~0ull;
         cnt = kept;
         for (int r = 0; r < k_c; ++r) {
-          if (tid == 0) min64[0] = ~0ull;
+          if (tid == 0) { min64[0] = ~0ull; min64[1] = ~0ull; }
           __syncthreads();
-          unsigned long long best = ~0ull;
-          for (uint32_t i = tid; i < clen; i += NT) {
-            const unsigned long long v = ((unsigned long long)keys[i] << 32) | (unsigned long long)(c0 + i);
-            if ((first || v > last) && keys[i] != 0xffffffffu && v < best) best = v;
-          }
           if (best != ~0ull) atomicMin(&min64[0], best);
           __syncthreads();
-          last  = min64[0];
-          first = false;
+          const unsigned long long last = min64[0];
           if (last == ~0ull) break;  // workgroup-uniform
           if (tid == 0) bc[cnt] = make_uint2((uint32_t)(last >> 32), (uint32_t)last);
           ++cnt;
+          const uint32_t owner = ((uint32_t)last - c0) % NT;
+          if (lane < kpt) {
+            const uint32_t v = owner + lane * NT;
+            if (v < clen) {
+              const uint32_t key = key_of(c0 + v);
+              const unsigned long long p = ((unsigned long long)key << 32) | (unsigned long long)(c0 + v);
+              if (key != 0xffffffffu && p > last) atomicMin(&min64[1], p);
+            }
+          }
+          __syncthreads();
+          if ((uint32_t)tid == owner) best = min64[1];
           __syncthreads();
         }
       }
@@ -2804,7 +2888,25 @@ static size_t head_smem_fixed(const ivf_pq_index& idx, int lut_mode, bool acc_ha
   return (size_t)idx.pq_dim * 256 * (lut32 ? 4 : 2) + 2 * 256 * 4 + 16 + 32 + 16 + (size_t)nt * 4 + 4 * (size_t)head_cand(k) * 4;
 }
 
-void pq3_head_scan(resources& res, const ivf_pq_index& idx, const pq3_head& h)
+// workgroups per CU the runtime grants a head kernel at its dynamic LDS size (asked once per kernel and size)
+static int head_occupancy(const void* fn, int nt, size_t smem)
+{
+  static std::mutex mu;
+  static std::map<std::pair<const void*, size_t>, int> known;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = known.find({fn, smem});
+  if (it != known.end()) return it->second;
+  hipFuncAttributes fa{};
+  HIP_TRY(hipFuncGetAttributes(&fa, fn));
+  CUVS_EXPECTS(fa.sharedSizeBytes == 0, "ivf_pq: the head kernel's LUT has to sit at LDS address 0");
+  int n = 0;
+  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, nt, smem));
+  CUVS_EXPECTS(n >= 1, "ivf_pq: the head kernel does not fit a CU");
+  known[{fn, smem}] = n;
+  return n;
+}
+
+int pq3_head_scan(resources& res, const ivf_pq_index& idx, const pq3_head& h)
 {
   head_params a{};
   a.items = static_cast<const work_item*>(h.items); a.item_begin = h.item_begin; a.item_end = h.item_end; a.n_lists = idx.n_lists;
@@ -2814,22 +2916,27 @@ void pq3_head_scan(resources& res, const ivf_pq_index& idx, const pq3_head& h)
   a.n_probes = h.n_probes; a.rot_dim = idx.rot_dim; a.k = h.k; a.is_ip = h.is_ip; a.pq_dim = idx.pq_dim;
   a.pq_len = idx.pq_len; a.book = idx.pq_book; a.per_cluster = idx.codebook_kind != 0 ? 1 : 0;
   a.filter_bits = h.filter_bits; a.indices = idx.indices.data(); a.stats = h.stats; a.hcand = head_cand((int)h.k);
-  // A LUT of up to 32 KiB (fp16 entries at pq_dim 64): two 512-thread workgroups per CU, one streams its list while the
-  // other selects; beyond: one 1024-thread workgroup. The rest of the LDS holds the score keys of a list chunk; longer
-  // lists are scanned in chunks.
+  // Workgroups per CU follow from the footprint: a workgroup's LDS is its LUT plus ~12 KiB (the score keys stay in registers),
+  // and the fp16-LUT variants fit the 80 registers of 6 waves per SIMD. A LUT of up to 32 KiB (fp16 entries at pq_dim 64):
+  // three 512-thread workgroups per CU - while one builds its LUT or selects, the others' gathers keep the LDS pipe busy; up to
+  // 64 KiB (fp32 entries at pq_dim 64): two; beyond: one 1024-thread workgroup. Longer lists are scanned in chunks.
   const bool lut32 = h.lut_mode == 0 || (h.lut_mode == 2 && !h.acc_half);
-  const bool small = (size_t)idx.pq_dim * 256 * (lut32 ? 4 : 2) <= 32 * 1024;
-  const int nt = small ? 512 : 1024;
-  const size_t budget = (small ? 80 : 160) * 1024 - 64, fixed = head_smem_fixed(idx, h.lut_mode, h.acc_half != 0, nt, (int)h.k);
-  CUVS_EXPECTS(budget > fixed + 4096, "ivf_pq: the head-phase LUT does not fit the LDS");
-  a.cap_rows = (uint32_t)(((budget - fixed) / 4) & ~size_t(63));
+  const size_t lut_bytes = (size_t)idx.pq_dim * 256 * (lut32 ? 4 : 2);
+  const bool nt512 = lut_bytes <= 64 * 1024;
+  const int nt = nt512 ? 512 : 1024;
+  const size_t smem = head_smem_fixed(idx, h.lut_mode, h.acc_half != 0, nt, (int)h.k);
+  CUVS_EXPECTS(smem <= 160 * 1024 - 64, "ivf_pq: the head-phase LUT does not fit the LDS");
+  a.cap_rows = (uint32_t)(kHeadRowsPerThread * nt);
   if (h.max_list_len > 0) a.cap_rows = std::min<uint32_t>(a.cap_rows, (uint32_t)round_up(h.max_list_len, 64));
-  const size_t smem   = fixed + (size_t)a.cap_rows * 4;
   a.one_shot          = h.one_shot;
   a.row_limit         = h.row_limit;
-  const unsigned grid = h.one_shot != 0u ? h.one_shot : pq3_grid(res) * (small ? 2u : 1u);
+  int wgs_per_cu = 0;
   auto go = [&](auto kern) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    const void* fn = reinterpret_cast<const void*>(kern);
+    HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    wgs_per_cu = head_occupancy(fn, nt, smem);
+    // the ticket form: as many workgroups as are resident
+    const unsigned grid = h.one_shot != 0u ? h.one_shot : pq3_grid(res) * (unsigned)wgs_per_cu;
     profile_begin(res, "pq_scan_kernel");
     profile_begin(res, "pq_head_kernel");
     hipLaunchKernelGGL(kern, dim3(grid), dim3(nt), smem, res.stream, a);
@@ -2839,12 +2946,15 @@ void pq3_head_scan(resources& res, const ivf_pq_index& idx, const pq3_head& h)
   auto pick = [&](auto lut_tag, auto acc_tag) {
     constexpr int LUT = decltype(lut_tag)::value;
     constexpr bool ACC = decltype(acc_tag)::value;
-    if (small) go(pq_head_kernel<LUT, ACC, 512>); else go(pq_head_kernel<LUT, ACC, 1024>);
+    constexpr bool L32 = LUT == 0 || (LUT == 2 && !ACC);
+    // (fp32 entries: the add chain's 126 registers - 4 waves per SIMD)
+    if (nt512) go(pq_head_kernel<LUT, ACC, 512, L32 ? 4 : 6>); else go(pq_head_kernel<LUT, ACC, 1024, 4>);
   };
   using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
   if (h.lut_mode == 0)      pick(I0{}, std::false_type{});
   else if (h.lut_mode == 1) { if (h.acc_half) pick(I1{}, std::true_type{}); else pick(I1{}, std::false_type{}); }
   else                      { if (h.acc_half) pick(I2{}, std::true_type{}); else pick(I2{}, std::false_type{}); }
+  return wgs_per_cu;
 }
 
 // up to 256 dimensions: pq_filter_kernel's FLAT build / flat_filter2_kernel; 256 / 384 / 512 / 768: the wide filter (ivf_pq_wide.hip)

@@ -82,7 +82,7 @@ struct pq3_head {
   uint32_t one_shot = 0;         // > 0: the number of items, one workgroup each (no tickets): the two-stream schedule's head launch
   uint32_t row_limit = 0;        // > 0: score only the first row_limit rows of a list (partial head: pq3_run::head_rows)
 };
-void pq3_head_scan(resources& res, const ivf_pq_index& idx, const pq3_head& h);
+int pq3_head_scan(resources& res, const ivf_pq_index& idx, const pq3_head& h);  // returns the workgroups per CU the launch gets
 
 // ---- IVF-Flat (fp32 or fp16 rows, L2) through the same filter: a derived fp16 copy of the rows' residuals laid out as MFMA operands
 struct flat3_cache {

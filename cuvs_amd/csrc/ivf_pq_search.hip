@@ -2330,12 +2330,12 @@ struct pq_search_ctx {
 };
 
 // ------------------------------------------------------------------ CUVS_AMD_SCAN_DEBUG reporting
-void report_head_stats(resources& res, const unsigned long long* d_stats)  // bit 2048
+void report_head_stats(resources& res, const unsigned long long* d_stats, int wgs_per_cu)  // bit 2048
 {
   auto hs = to_host(res, d_stats, 8);
   const double n = (double)std::max<unsigned long long>(1, hs[5]);
-  fprintf(stderr, "[pq_head] items %llu; workgroup cycles per item: header %.0f, LUT %.0f, scores %.0f, select %.0f, output %.0f\n", hs[5],
-          hs[0] / n, hs[1] / n, hs[2] / n, hs[3] / n, hs[4] / n);
+  fprintf(stderr, "[pq_head] items %llu; workgroup cycles per item: header %.0f, LUT %.0f, scores %.0f, select %.0f, output %.0f; "
+          "workgroups per CU %d\n", hs[5], hs[0] / n, hs[1] / n, hs[2] / n, hs[3] / n, hs[4] / n, wgs_per_cu);
 }
 
 void report_filter_stats(resources& res, const unsigned long long* d_stats, const uint32_t* counters)  // bit 1024
@@ -2418,7 +2418,7 @@ void launch_lut_scan(resources& res, const pq_search_plan& pl, const scan_args& 
   }
 }
 
-// single-pair work items (pq3_head_scan): scores of the whole list in LDS, k smallest selected there
+// single-pair work items (pq3_head_scan): one workgroup scores the whole list and selects its k smallest
 void launch_head_scan(const pq_search_ctx& c, const scan_args& sa)
 {
   pq3_head h{};
@@ -2430,8 +2430,8 @@ void launch_head_scan(const pq_search_ctx& c, const scan_args& sa)
   dev_buf<unsigned long long> hst(c.res, (sa.dbg & 2048) ? 8 : 0);
   if (sa.dbg & 2048) HIP_TRY(hipMemsetAsync(hst.data(), 0, hst.bytes(), c.res.stream));
   h.stats = hst.data();
-  pq3_head_scan(c.res, c.idx, h);
-  if (sa.dbg & 2048) report_head_stats(c.res, hst.data());
+  const int wgs_per_cu = pq3_head_scan(c.res, c.idx, h);
+  if (sa.dbg & 2048) report_head_stats(c.res, hst.data(), wgs_per_cu);
 }
 
 // the tail phase on the matrix cores (pq_filter_kernel / pq_filter4_kernel, or the wide filter), the LUT scan of the queries the
