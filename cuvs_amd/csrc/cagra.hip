@@ -1493,27 +1493,116 @@ void cagra_search(resources& res, const cagra_index& idx, const cuvsCagraSearchP
 }
 
 // ------------------------------------------------------------------ extend (add_nodes.cuh)
-// New rows are added chunk by chunk: every new node searches the CURRENT graph (so later chunks can link to
-// earlier ones) and takes the `degree` nearest results as its edges; each existing node that was picked gives its
-// last (weakest-ranked) edges - at most degree/2 of them, one atomic slot counter per node - to the new nodes that
-// picked it, which is how the reference wires the reverse edges (add_nodes.cuh: rev edges replace the tail of the
-// list). The dataset and the graph become storage owned by the index.
-__global__ void extend_rows_kernel(const uint32_t* __restrict__ nb, int64_t m, uint32_t degree, int64_t n_cur,
-                                   uint32_t* __restrict__ graph, uint32_t* __restrict__ rev_cnt)
+// the fields cuvsCagraSearchParamsCreate fills in (c/src/neighbors/cagra.cpp: the defaults of cagra::search_params)
+static cuvsCagraSearchParams cagra_default_search_params()
 {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= m * (int64_t)degree) return;
-  const int64_t v = i / degree;
-  const uint32_t j = (uint32_t)(i % degree);
-  uint32_t u = nb[i];
-  if (u >= (uint32_t)n_cur) u = (uint32_t)((v * 2654435761ull + j) % (uint64_t)n_cur);  // search gave fewer results
-  graph[(n_cur + v) * degree + j] = u;
-  if (j < degree / 2) {  // the closer half of the new node's neighbours get a reverse edge
-    const uint32_t slot = atomicAdd(&rev_cnt[u], 1u);
-    if (slot < degree / 2) graph[(int64_t)u * degree + (degree - 1 - slot)] = (uint32_t)(n_cur + v);
+  cuvsCagraSearchParams p{};
+  p.itopk_size              = 64;
+  p.search_width            = 1;
+  p.algo                    = AUTO;
+  p.hashmap_mode            = AUTO_HASH;
+  p.hashmap_max_fill_rate   = 0.5f;
+  p.num_random_samplings    = 1;
+  p.rand_xor_mask           = 0x128394;
+  p.persistent              = false;
+  p.persistent_lifetime     = 2;
+  p.persistent_device_usage = 1.0f;
+  return p;
+}
+
+// add_node_core (add_nodes.cuh:24-277) for one chunk: rows n_cur .. n_cur + cm of the host graph `g` ([>= n_cur + cm, degree],
+// rows below n_cur filled) from `cand` [cm, 2 degree], the walk's results of the chunk's rows over the first n_cur rows
+// (invalid: any id >= n_cur). Integer bookkeeping only; tests/cagra_extend_ref.py restates it line for line.
+static void cagra_add_nodes_host(std::vector<uint32_t>& g, const std::vector<uint32_t>& cand, int64_t n_cur, int64_t cm, uint32_t degree)
+{
+  const uint32_t K = 2 * degree, half = degree / 2;
+  const uint64_t n_new = (uint64_t)(n_cur + cm);  // the reference's new_size: rows once this chunk is in
+  // step 0 (:40-53): incoming edges of every row of the graph the chunk starts from
+  std::vector<uint32_t> incoming((size_t)n_new, 0u);
+  for (size_t e = 0; e < (size_t)n_cur * degree; ++e)
+    if (g[e] < n_new) ++incoming[g[e]];
+  // step 2 (:148-189): the detour count of candidate i is the number of valid candidates j < i whose list holds i; an
+  // invalid id gets 2 degree + 1. The lists read are those of rows below n_cur, which step 3 has not touched yet. The
+  // reference sorts with std::sort, which leaves ties open; here the sort is stable (nearest first among equal counts).
+  std::vector<std::pair<uint32_t, uint32_t>> by_id(K);  // (id, position among the candidates), sorted: id -> positions
+  std::vector<uint32_t> count(K), last_j(K), order(K);
+  for (int64_t v = 0; v < cm; ++v) {
+    const uint32_t* c = cand.data() + (size_t)v * K;
+    for (uint32_t i = 0; i < K; ++i) {
+      by_id[i]  = {c[i], i};
+      count[i]  = (int64_t)c[i] < n_cur ? 0u : K + 1;
+      last_j[i] = 0xffffffffu;
+      order[i]  = i;
+    }
+    std::sort(by_id.begin(), by_id.end());
+    for (uint32_t j = 0; j < K; ++j) {
+      if ((int64_t)c[j] >= n_cur) continue;
+      const uint32_t* row = g.data() + (size_t)c[j] * degree;
+      for (uint32_t k = 0; k < degree; ++k) {
+        auto it = std::lower_bound(by_id.begin(), by_id.end(), std::make_pair(row[k], 0u));
+        for (; it != by_id.end() && it->first == row[k]; ++it) {
+          const uint32_t i = it->second;
+          if (i > j && (int64_t)c[i] < n_cur && last_j[i] != j) { last_j[i] = j; ++count[i]; }  // once per (j, i) (:168-174)
+        }
+      }
+    }
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return count[a] < count[b]; });
+    uint32_t* mine = g.data() + (size_t)(n_cur + v) * degree;
+    for (uint32_t i = 0; i < degree; ++i) mine[i] = c[order[i]];
+  }
+  // step 3 (:191-275), row after row: each of the row's degree / 2 first targets gives up the neighbour of its list's tail
+  // half that has strictly the most incoming edges (and was not taken for this row yet); the row's own list is its rank
+  // list and the evicted ids in turns
+  std::vector<uint32_t> rev(half), temp(degree);
+  for (int64_t v = 0; v < cm; ++v) {
+    const uint32_t me = (uint32_t)(n_cur + v);
+    uint32_t* mine    = g.data() + (size_t)me * degree;
+    for (uint32_t i = 0; i < half; ++i) {
+      const uint32_t target = mine[i];
+      if (target >= n_new) CUVS_FAIL("Invalid node ID found in updated_graph (%u)", target);
+      uint32_t take_id = (uint32_t)n_new, take_slot = 0, take_count = 0;
+      uint32_t* trow = g.data() + (size_t)target * degree;
+      for (int32_t j = (int32_t)degree - 1; j >= (int32_t)half; --j) {
+        const uint32_t nb = trow[j];
+        if (nb >= n_new) CUVS_FAIL("Invalid node ID found in updated_graph (%u)", nb);
+        if (incoming[nb] > take_count && std::find(rev.begin(), rev.begin() + i, nb) == rev.begin() + i) {
+          take_count = incoming[nb];
+          take_id    = nb;
+          take_slot  = (uint32_t)j;
+        }
+      }
+      trow[take_slot] = me;
+      rev[i]          = take_id;
+    }
+    incoming[me] = half;
+    uint32_t pos[2] = {0, 0}, turn = 0, n_add = 0;
+    const uint32_t* list[2] = {mine, rev.data()};
+    const uint32_t len[2]   = {degree, half};
+    while (n_add < degree && (pos[0] < degree || pos[1] < half)) {
+      for (; pos[turn] < len[turn]; ++pos[turn]) {
+        const uint32_t cnd = list[turn][pos[turn]];
+        if (cnd >= n_new) continue;
+        if (std::find(temp.begin(), temp.begin() + n_add, cnd) != temp.begin() + n_add) continue;
+        temp[n_add++] = cnd;  // (the position stays, as in the reference: the entry is a duplicate at the next turn)
+        break;
+      }
+      turn = 1 - turn;
+    }
+    if (n_add < degree)
+      CUVS_FAIL("Number of edges is not enough (target_new_node_id:%lu, num_add:%lu, degree:%lu)", (unsigned long)me, (unsigned long)n_add,
+                (unsigned long)degree);
+    std::copy(temp.begin(), temp.end(), mine);
   }
 }
 
+// New rows are added chunk by chunk as in the reference (add_graph_nodes, add_nodes.cuh:279-344): every row of a chunk walks
+// the graph of the old rows and the chunks before it for its 2 degree nearest rows (itopk max(4 degree, 256)); the candidates
+// are re-ordered by detour count, each of the row's degree / 2 first targets gets a reverse edge in place of the tail
+// neighbour with the most incoming edges, and the row's list interleaves its rank list with the evicted ids. The walk runs on
+// the device; the re-ordering and the reverse edges are done on the host over a host copy of the graph, as in the reference.
+// One deviation: the reference searches with default parameters, whose AUTO may pick the multi-CTA walk, which races for
+// parents; the walk here is always the single-workgroup one, so the graph is reproducible (and pinned by a CPU twin).
+// The new dataset and graph are built on the side and become the index's only when every chunk has succeeded.
 void cagra_extend(resources& res, cagra_index& idx, const void* new_rows, bool new_is_host, int64_t m, uint32_t max_chunk)
 {
   // the walk below reports source ids and the new rows would have none: the reference's add_nodes.cuh defines nothing for an
@@ -1524,44 +1613,58 @@ void cagra_extend(resources& res, cagra_index& idx, const void* new_rows, bool n
   CUVS_EXPECTS(idx.n + m < (int64_t(1) << 32) - 1, "cagra: at most 2^32 - 2 rows (uint32 graph)");
   const size_t esz = elem_size(idx.dtype), row_bytes = (size_t)idx.dim * esz;
   const int64_t n0 = idx.n, n1 = idx.n + m;
-  auto data  = dev_buf<char>::persistent((size_t)n1 * row_bytes);
-  auto graph = dev_buf<uint32_t>::persistent((size_t)n1 * idx.degree);
-  copy_async(res, data.data(), idx.data, (size_t)n0 * row_bytes);
-  copy_async(res, data.data() + (size_t)n0 * row_bytes, new_rows, (size_t)m * row_bytes);
-  copy_async(res, graph.data(), idx.graph.data(), (size_t)n0 * idx.degree * sizeof(uint32_t));
+  const uint32_t degree = idx.degree, K = 2 * degree;
+  cagra_index ext;  // the extended index, on the side
+  ext.metric = idx.metric; ext.dtype = idx.dtype; ext.dim = idx.dim; ext.degree = degree;
+  ext.owned  = dev_buf<char>::persistent((size_t)n1 * row_bytes);
+  ext.data   = ext.owned.data();
+  ext.graph  = dev_buf<uint32_t>::persistent((size_t)n1 * degree);
+  std::vector<uint32_t> g((size_t)n1 * degree, kInvalidNode);
+  copy_async(res, ext.owned.data(), idx.data, (size_t)n0 * row_bytes);
+  // rows the device cannot reach are host rows; anything else (device, pinned or managed memory) is left to the runtime to place
+  HIP_TRY(hipMemcpyAsync(ext.owned.data() + (size_t)n0 * row_bytes, new_rows, (size_t)m * row_bytes,
+                         new_is_host ? hipMemcpyHostToDevice : hipMemcpyDefault, res.stream));
+  copy_async(res, g.data(), idx.graph.data(), (size_t)n0 * degree * sizeof(uint32_t));
   sync(res);
-  (void)new_is_host;
-  idx.owned = std::move(data);
-  idx.data  = idx.owned.data();
-  idx.graph = std::move(graph);
-  const int64_t chunk = std::max<int64_t>(1, max_chunk == 0 ? 8192 : (int64_t)max_chunk);
-  cuvsCagraSearchParams sp{};
-  sp.itopk_size   = std::max<size_t>(64, 2 * (size_t)idx.degree);
-  sp.search_width = 2;
-  sp.algo         = SINGLE_CTA;  // k = degree may exceed what a 32-entry walker list can return
-  sp.hashmap_max_fill_rate = 0.5f;
-  sp.num_random_samplings  = 1;
-  sp.rand_xor_mask         = 0x128394;
-  dev_buf<uint32_t> nb(res, (size_t)chunk * idx.degree), rev_cnt(res, n1);
-  dev_buf<float> nd(res, (size_t)chunk * idx.degree);
-  // reverse-edge slots are counted over the whole call: a later chunk must not overwrite the reverse edges an
-  // earlier chunk placed in the same list tail
-  HIP_TRY(hipMemsetAsync(rev_cnt.data(), 0, rev_cnt.bytes(), res.stream));
+  cuvsCagraSearchParams sp = cagra_default_search_params();
+  sp.itopk_size            = std::max<size_t>(4 * (size_t)degree, 256);  // add_nodes.cuh:69-70
+  sp.algo                  = SINGLE_CTA;
+  const int64_t chunk = max_chunk == 0 ? m : (int64_t)max_chunk;  // 0: one chunk (add_nodes.cuh:297-298)
+  const int64_t batch = std::min<int64_t>(chunk, 65536);          // queries per launch (the chunk decides the graph, not this)
+  dev_buf<uint32_t> nb(res, (size_t)batch * K);
+  dev_buf<float> nd(res, (size_t)batch * K);
+  std::vector<uint32_t> cand, got;
   for (int64_t c0 = 0; c0 < m; c0 += chunk) {
     const int64_t cm = std::min(chunk, m - c0);
-    idx.n = n0 + c0;              // the graph searched by this chunk: old rows + the chunks before it
-    cagra_set_norms(res, idx);    // cosine: |x| of everything searchable so far
-    const int k = (int)std::min<int64_t>(idx.degree, idx.n);
-    cagra_search(res, idx, sp, static_cast<const char*>(idx.data) + (size_t)idx.n * row_bytes, cm, k, nb.data(), false,
-                 nd.data(), nullptr);
-    if (k < (int)idx.degree) CUVS_FAIL("cagra::extend: the index must hold at least graph_degree rows");
-    hipLaunchKernelGGL(extend_rows_kernel, dim3(grid_blocks(cm * (int64_t)idx.degree, 256)), dim3(256), 0, res.stream,
-                       nb.data(), cm, idx.degree, idx.n, idx.graph.data(), rev_cnt.data());
-    HIP_TRY(hipGetLastError());
+    ext.n = n0 + c0;              // the graph searched by this chunk: old rows + the chunks before it
+    cagra_set_norms(res, ext);    // cosine: |x| of everything searchable so far
+    copy_async(res, ext.graph.data(), g.data(), (size_t)ext.n * degree * sizeof(uint32_t));
+    const int k = (int)std::min<int64_t>(K, ext.n);  // a graph of fewer than 2 degree rows: the missing columns stay invalid
+    cand.assign((size_t)cm * K, kInvalidNode);
+    for (int64_t b0 = 0; b0 < cm; b0 += batch) {
+      const int64_t bm = std::min(batch, cm - b0);
+      cagra_search(res, ext, sp, static_cast<const char*>(ext.data) + (size_t)(ext.n + b0) * row_bytes, bm, k, nb.data(), false,
+                   nd.data(), nullptr);
+      got.resize((size_t)bm * k);
+      copy_async(res, got.data(), nb.data(), got.size() * sizeof(uint32_t));
+      sync(res);
+      for (int64_t v = 0; v < bm; ++v)
+        for (int j = 0; j < k; ++j) {
+          const uint32_t id = got[(size_t)v * k + j];
+          if ((int64_t)id < ext.n) cand[(size_t)(b0 + v) * K + j] = id;  // add_nodes.cuh:129,158: anything else is invalid
+        }
+    }
+    cagra_add_nodes_host(g, cand, ext.n, cm, degree);
   }
-  idx.n = n1;
-  cagra_set_norms(res, idx);
+  copy_async(res, ext.graph.data(), g.data(), g.size() * sizeof(uint32_t));
+  ext.n = n1;
+  cagra_set_norms(res, ext);
   sync(res);
+  idx.owned = std::move(ext.owned);
+  idx.data  = idx.owned.data();
+  idx.graph = std::move(ext.graph);
+  idx.norms = std::move(ext.norms);
+  idx.n     = n1;
 }
 
 // rows of bytes -> [n, 8 dim] floats of their bits (bit j of byte b -> column 8 b + j): squared L2 over them is the Hamming
@@ -2030,18 +2133,8 @@ cuvsError_t cuvsCagraExtendParamsDestroy(cuvsCagraExtendParams_t params)
 cuvsError_t cuvsCagraSearchParamsCreate(cuvsCagraSearchParams_t* params)
 {
   return (cuvsError_t)translate_exceptions([=] {
-    auto* p                  = new cuvsCagraSearchParams{};
-    p->itopk_size            = 64;
-    p->search_width          = 1;
-    p->algo                  = AUTO;
-    p->hashmap_mode          = AUTO_HASH;
-    p->hashmap_max_fill_rate = 0.5f;
-    p->num_random_samplings  = 1;
-    p->rand_xor_mask         = 0x128394;
-    p->persistent            = false;
-    p->persistent_lifetime   = 2;
-    p->persistent_device_usage = 1.0f;
-    *params                  = p;
+    auto* p = new cuvsCagraSearchParams(cagra_default_search_params());
+    *params = p;
   });
 }
 cuvsError_t cuvsCagraSearchParamsDestroy(cuvsCagraSearchParams_t params)
@@ -2441,6 +2534,7 @@ cuvsError_t cuvsCagraExtend(cuvsResources_t res_h, cuvsCagraExtendParams_t param
     auto& t = additional_dataset->dl_tensor;
     CUVS_EXPECTS(t.ndim == 2 && is_c_contiguous(t) && t.shape[1] == idx.dim, "additional_dataset must be [m, dim] row-major");
     CUVS_EXPECTS(elem_of(t.dtype) == idx.dtype, "additional_dataset dtype differs from the index dtype");
+    CUVS_EXPECTS(is_device_accessible(t) || is_host_accessible(t), "additional_dataset must be accessible on host or device memory");
     cagra_extend(res, idx, dl_data(t), !is_device_accessible(t), t.shape[0], params ? params->max_chunk_size : 0u);
   });
 }

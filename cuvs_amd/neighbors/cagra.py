@@ -231,8 +231,9 @@ class _CExtendParams(C.Structure):
 
 @auto_sync_resources
 def extend(index, additional_dataset, max_chunk_size=0, resources=None):
-    """cuvsCagraExtend: add rows to a built index (reference: python/cuvs/cuvs/neighbors/cagra extend). The index
-    owns its dataset afterwards. An index loaded from a file that carries source_indices is refused: the new rows would have
+    """cuvsCagraExtend: add rows (a device tensor or a host array) to a built index by the rules of the reference's add_nodes.cuh
+    (reference: python/cuvs/cuvs/neighbors/cagra extend); max_chunk_size rows at a time, 0 = all at once. The graph is
+    reproducible (tests/cagra_extend_ref.py restates it). The index owns its dataset afterwards; a failed call leaves it as it was. An index loaded from a file that carries source_indices is refused: the new rows would have
     no source id (the reference's add_nodes.cuh defines nothing for it)."""
     ds = additional_dataset.contiguous() if isinstance(additional_dataset, torch.Tensor) else np.ascontiguousarray(additional_dataset)
     p = C.POINTER(_CExtendParams)()
