@@ -2032,6 +2032,29 @@ void cagra_index_info(uintptr_t addr, int64_t* size, int* metric)
   *metric   = idx->metric;
 }
 
+// hnsw.hip: what the conversion to HNSW reads of the index behind a cuvsCagraIndex handle
+cagra_view cagra_index_view(uintptr_t addr)
+{
+  CUVS_EXPECTS(addr != 0, "CAGRA index is not built");
+  auto* idx = reinterpret_cast<const cagra_index*>(addr);
+  return cagra_view{idx->metric, idx->dtype, idx->n, idx->dim, idx->degree, idx->data, idx->graph.data(), idx->vpq.on()};
+}
+
+// hnsw.hip: the kNN graph of rows among themselves by the build's own size rule (cagra_knn_graph under the default build_algo)
+void cagra_rows_knn_graph(resources& res, const void* data, elem_t et, int64_t n, int64_t dim, uint32_t K, int metric, uint32_t* knn)
+{
+  cagra_index rows;
+  rows.metric = metric;
+  rows.dtype  = et;
+  rows.n      = n;
+  rows.dim    = dim;
+  rows.data   = data;
+  cuvsCagraIndexParams p{};
+  p.metric     = (cuvsDistanceType)metric;
+  p.build_algo = IVF_PQ;
+  cagra_knn_graph(res, p, rows, K, knn);
+}
+
 // tiered_index.hip: the rows a viewing index was built over have moved (same bytes, new address)
 void cagra_repoint_dataset(uintptr_t addr, const void* data)
 {

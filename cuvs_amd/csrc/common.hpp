@@ -109,6 +109,8 @@ struct tuning {
   bool cagra_auto_multi = false;  // CUVS_AMD_CAGRA_AUTO=multi
   int tiered_path       = 0;      // CUVS_AMD_TIERED_PATH=composed | fused: the tail phase of a tiered search always through the composed path (threshold append + merge kernel; comparator) or, where its shapes allow, the single-launch kernel
   bool native_format    = false;  // CUVS_AMD_NATIVE_FORMAT=1: *Serialize writes this library's own container
+  int hnsw_pack_rows    = 0;      // CUVS_AMD_HNSW_PACK_ROWS: rows per chunk of the level-0 record packing of cuvsHnswFromCagra (test hook: several chunks on a small index)
+  int hnsw_pack_host    = 0;      // CUVS_AMD_HNSW_PACK_HOST=1: the records are interleaved by the host loop instead of hnsw_pack_kernel (comparator of the timing and of the tests)
 };
 tuning load_tuning_from_env();
 

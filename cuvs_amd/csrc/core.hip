@@ -222,6 +222,8 @@ tuning load_tuning_from_env()
   if (const char* e = getenv("CUVS_AMD_CAGRA_AUTO")) t.cagra_auto_multi = e[0] == 'm';
   if (const char* e = getenv("CUVS_AMD_TIERED_PATH")) t.tiered_path = strcmp(e, "composed") == 0 ? 1 : (strcmp(e, "fused") == 0 ? 2 : 0);
   if (const char* e = getenv("CUVS_AMD_NATIVE_FORMAT")) t.native_format = e[0] == '1';
+  t.hnsw_pack_rows   = geti("CUVS_AMD_HNSW_PACK_ROWS", 0);
+  t.hnsw_pack_host   = geti("CUVS_AMD_HNSW_PACK_HOST", 0);
   return t;
 }
 

@@ -149,4 +149,20 @@ void cagra_index_info(uintptr_t addr, int64_t* size, int* metric);
 // a CAGRA index that views its rows (built from a device dataset) follows them to a new address holding the same bytes
 void cagra_repoint_dataset(uintptr_t addr, const void* data);
 
+// ---------------------------------------------------------------- hnsw.hip helpers (defined in cagra.hip)
+// the index behind a cuvsCagraIndex handle: device rows (null when the index holds VPQ codes only) and device graph [n, degree]
+struct cagra_view {
+  int metric;
+  elem_t dtype;
+  int64_t n, dim;
+  uint32_t degree;
+  const void* data;
+  const uint32_t* graph;
+  bool vpq;
+};
+cagra_view cagra_index_view(uintptr_t addr);
+// kNN graph [n, K] of device rows among themselves (uint32 ids ascending by distance, self excluded, 0xffffffff = none) by the
+// CAGRA build's size rule: exact tiled brute force up to 200000 rows, IVF-PQ + refine above
+void cagra_rows_knn_graph(resources& res, const void* data, elem_t et, int64_t n, int64_t dim, uint32_t K, int metric, uint32_t* knn);
+
 }  // namespace cuvs_amd

@@ -26,3 +26,6 @@
 #include <cuvs/neighbors/mg_ivf_pq.h>
 #include <cuvs/neighbors/mg_cagra.h>
 #endif
+#ifdef CUVS_BUILD_CAGRA_HNSWLIB
+#include <cuvs/neighbors/hnsw.h>
+#endif
