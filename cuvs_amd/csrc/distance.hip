@@ -631,7 +631,7 @@ void pairwise_distance(resources& res, const TQ* q, int64_t m, int64_t ldq, cons
   CUVS_EXPECTS((m + BM - 1) / BM <= 65535, "pairwise_distance: too many query rows per call");
   bool vec = vec_ok(q, ldq, dim) && vec_ok(x, ldx, dim);
   if constexpr (std::is_same_v<TQ, TX> && (sizeof(TQ) == 4 || sizeof(TQ) == 2)) {
-    if (vec && dim % BK == 0 && !res.tune.dist_old) {
+    if (vec && dim > 0 && dim % BK == 0 && !res.tune.dist_old) {  // dim 0: the tile kernel's first load is unconditional
       launch_tile<TQ, TX, 0>(metric, grid, res.stream, q, m, ldq, x, n, ldx, dim, ep, out, ldo, append_args{});
       HIP_TRY(hipGetLastError());
       return;
@@ -655,7 +655,7 @@ bool pairwise_distance_grouped(resources& res, const float* q, int64_t m, int64_
                                int64_t ldg)
 {
   if (m == 0 || n == 0) return true;
-  if (!(vec_ok(q, ldq, dim) && vec_ok(x, ldx, dim) && dim % BK == 0) || res.tune.dist_old) return false;
+  if (!(vec_ok(q, ldq, dim) && vec_ok(x, ldx, dim) && dim > 0 && dim % BK == 0) || res.tune.dist_old) return false;
   if ((m + BM - 1) / BM > 65535 || ldo % 4 != 0 || (reinterpret_cast<uintptr_t>(out) & 15) != 0) return false;
   CUVS_EXPECTS(ldo >= round_up(n, BN) && ldg * 16 >= round_up(n, BN), "pairwise_distance_grouped: row pitch");
   CUVS_EXPECTS(metric == M_InnerProduct || (qn && xn), "pairwise_distance_grouped: norms required");
@@ -709,7 +709,7 @@ void pairwise_threshold_append(resources& res, const TQ* q, int64_t m, int64_t l
   const int64_t blocks     = (supertiles + 7) / 8 * 8 * (int64_t)(ap.srt * ap.sct);
   CUVS_EXPECTS(blocks < (int64_t(1) << 31), "pairwise_threshold_append: grid too large");
   const bool vec = vec_ok(q, ldq, dim) && vec_ok(x, ldx, dim);
-  if (vec && dim % BK == 0 && !res.tune.dist_old) {
+  if (vec && dim > 0 && dim % BK == 0 && !res.tune.dist_old) {
     dev_buf<unsigned long long> stats;
     if (ap.dbg & 4) {
       stats = dev_buf<unsigned long long>(res, 4);
@@ -820,6 +820,63 @@ extern "C" __attribute__((visibility("default"))) int cuvsAmdFusedArgmin(uintptr
   });
 }
 
+// Typed test hooks (not in the reference ABI): every built instance of pairwise_distance / fused_l2_argmin with the caller's
+// pointers and pitches, so that tests/ can reach each load path (views into wider buffers, offset base pointers, an output
+// pitch beyond n). dtype codes: 0 float, 1 __half, 2 int8_t, 3 uint8_t.
+namespace {
+template <typename TQ, typename TX>
+void pairwise_hook(cuvs_amd::resources& r, const void* q, int64_t ldq, int64_t m, const void* x, int64_t ldx, int64_t n, int64_t dim,
+                   int metric, float* out, int64_t ldo)
+{
+  using namespace cuvs_amd;
+  dev_buf<float> qn(r, m), xn(r, n);
+  if (metric != M_InnerProduct) {
+    row_norms<TQ>(r, static_cast<const TQ*>(q), m, dim, ldq, qn.data(), metric == M_CosineExpanded);
+    row_norms<TX>(r, static_cast<const TX*>(x), n, dim, ldx, xn.data(), metric == M_CosineExpanded);
+  }
+  pairwise_distance<TQ, TX>(r, static_cast<const TQ*>(q), m, ldq, static_cast<const TX*>(x), n, ldx, dim, qn.data(), xn.data(),
+                            metric, out, ldo);
+}
+}  // namespace
+
+extern "C" __attribute__((visibility("default"))) int cuvsAmdPairwiseDistanceTyped(uintptr_t res, const void* q, int q_dtype,
+                                                                                    int64_t ldq, int64_t m, const void* x,
+                                                                                    int x_dtype, int64_t ldx, int64_t n,
+                                                                                    int64_t dim, int metric, float* out,
+                                                                                    int64_t ldo)
+{
+  using namespace cuvs_amd;
+  return translate_exceptions([=] {
+    auto& r = *as_res(res);
+    CUVS_EXPECTS(metric_supported(metric), "cuvsAmdPairwiseDistanceTyped: unsupported metric %d", metric);
+    if (q_dtype == 0 && x_dtype == 0) pairwise_hook<float, float>(r, q, ldq, m, x, ldx, n, dim, metric, out, ldo);
+    else if (q_dtype == 1 && x_dtype == 1) pairwise_hook<__half, __half>(r, q, ldq, m, x, ldx, n, dim, metric, out, ldo);
+    else if (q_dtype == 1 && x_dtype == 0) pairwise_hook<__half, float>(r, q, ldq, m, x, ldx, n, dim, metric, out, ldo);
+    else if (q_dtype == 2 && x_dtype == 0) pairwise_hook<int8_t, float>(r, q, ldq, m, x, ldx, n, dim, metric, out, ldo);
+    else if (q_dtype == 3 && x_dtype == 0) pairwise_hook<uint8_t, float>(r, q, ldq, m, x, ldx, n, dim, metric, out, ldo);
+    else CUVS_FAIL("cuvsAmdPairwiseDistanceTyped: no instance for dtypes (%d, %d)", q_dtype, x_dtype);
+  });
+}
+
+extern "C" __attribute__((visibility("default"))) int cuvsAmdFusedArgminTyped(uintptr_t res, const void* q, int q_dtype, int64_t ldq,
+                                                                               int64_t m, const float* centers, int64_t n,
+                                                                               int64_t dim, uint32_t* labels, float* min_val)
+{
+  using namespace cuvs_amd;
+  return translate_exceptions([=] {
+    auto& r = *as_res(res);
+    dev_buf<float> cn(r, n);
+    row_norms<float>(r, centers, n, dim, dim, cn.data(), false);
+    switch (q_dtype) {
+      case 0: fused_l2_argmin<float>(r, static_cast<const float*>(q), m, ldq, centers, n, dim, cn.data(), labels, min_val); break;
+      case 1: fused_l2_argmin<__half>(r, static_cast<const __half*>(q), m, ldq, centers, n, dim, cn.data(), labels, min_val); break;
+      case 2: fused_l2_argmin<int8_t>(r, static_cast<const int8_t*>(q), m, ldq, centers, n, dim, cn.data(), labels, min_val); break;
+      case 3: fused_l2_argmin<uint8_t>(r, static_cast<const uint8_t*>(q), m, ldq, centers, n, dim, cn.data(), labels, min_val); break;
+      default: CUVS_FAIL("cuvsAmdFusedArgminTyped: no instance for dtype %d", q_dtype);
+    }
+  });
+}
+
 // Timing hook for the threshold-append tile kernel alone: thresholds that nothing beats, `reps` launches between two
 // events. dbg != 0 switches parts of the main loop off (results are wrong; only the duration means anything).
 extern "C" __attribute__((visibility("default"))) int cuvsAmdTileBench(uintptr_t res, int64_t m, int64_t n, int64_t dim,
@@ -907,11 +964,14 @@ void pairwise_colmajor(cuvs_amd::resources& res, const T* xp, int64_t m, const T
   using namespace cuvs_amd;
   CUVS_EXPECTS(m <= int64_t(65535) * 64 && n <= int64_t(65535) * 64, "cuvsPairwiseDistance: too many rows for the column-major path");
   dev_buf<T> xr(res, (size_t)m * dim), yr(res, (size_t)n * dim);
-  hipLaunchKernelGGL((colmajor_to_rowmajor_kernel<T>), dim3((unsigned)((dim + 63) / 64), (unsigned)((m + 63) / 64)),
-                     dim3(256), 0, res.stream, xp, xr.data(), m, dim);
-  hipLaunchKernelGGL((colmajor_to_rowmajor_kernel<T>), dim3((unsigned)((dim + 63) / 64), (unsigned)((n + 63) / 64)),
-                     dim3(256), 0, res.stream, yp, yr.data(), n, dim);
-  HIP_TRY(hipGetLastError());
+  if (m == 0 || n == 0) return;
+  if (dim > 0) {  // nothing to re-lay without columns (and a grid of 0 blocks is no launch)
+    hipLaunchKernelGGL((colmajor_to_rowmajor_kernel<T>), dim3((unsigned)((dim + 63) / 64), (unsigned)((m + 63) / 64)),
+                       dim3(256), 0, res.stream, xp, xr.data(), m, dim);
+    hipLaunchKernelGGL((colmajor_to_rowmajor_kernel<T>), dim3((unsigned)((dim + 63) / 64), (unsigned)((n + 63) / 64)),
+                       dim3(256), 0, res.stream, yp, yr.data(), n, dim);
+    HIP_TRY(hipGetLastError());
+  }
   pairwise_typed<T>(res, yr.data(), n, xr.data(), m, dim, metric, out);
 }
 }  // namespace
@@ -932,8 +992,11 @@ extern "C" cuvsError_t cuvsPairwiseDistance(cuvsResources_t res_h, DLManagedTens
     CUVS_EXPECTS(x.dtype.code == y.dtype.code && x.dtype.bits == y.dtype.bits,
                  "Inputs to cuvsPairwiseDistance must all have the same dtype");
     CUVS_EXPECTS(x.ndim == 2 && y.ndim == 2 && d.ndim == 2, "Inputs to cuvsPairwiseDistance must be matrices");
-    const bool c_order = is_c_contiguous(x) && is_c_contiguous(y) && is_c_contiguous(d);
-    const bool f_order = is_f_contiguous(x) && is_f_contiguous(y) && is_f_contiguous(d);
+    // a matrix without elements has no layout to disagree with (frameworks give a zero extent strides of their own choosing)
+    auto c_ok = [](const DLTensor& t) { return t.shape[0] == 0 || t.shape[1] == 0 || is_c_contiguous(t); };
+    auto f_ok = [](const DLTensor& t) { return t.shape[0] == 0 || t.shape[1] == 0 || is_f_contiguous(t); };
+    const bool c_order = c_ok(x) && c_ok(y) && c_ok(d);
+    const bool f_order = f_ok(x) && f_ok(y) && f_ok(d);
     CUVS_EXPECTS(c_order || f_order,
                  "Inputs to cuvsPairwiseDistance must all have the same layout (row-major or col-major)");
     const int64_t m = x.shape[0], n = y.shape[0], dim = x.shape[1];

@@ -26,7 +26,8 @@ DISTANCE_TYPES = {
 }
 DISTANCE_NAMES = {v: k for k, v in DISTANCE_TYPES.items()}
 
-SUPPORTED_DISTANCES = ["euclidean", "l2", "sqeuclidean", "inner_product", "cosine"]  # what the HIP library builds
+SUPPORTED_DISTANCES = ["euclidean", "l2", "sqeuclidean", "inner_product", "cosine",
+                       "l2_unexpanded", "l2_sqrt_unexpanded"]  # what the HIP library builds
 
 
 def pairwise_distance(X, Y, out=None, metric="euclidean", p=2.0, resources=None):

@@ -11,7 +11,8 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
-METRICS = {"sqeuclidean": 0, "euclidean": 1, "l2": 1, "cosine": 2, "inner_product": 6}
+METRICS = {"sqeuclidean": 0, "euclidean": 1, "l2": 1, "cosine": 2, "l2_unexpanded": 4, "l2_sqrt_unexpanded": 5,
+           "inner_product": 6}
 
 
 def lib():

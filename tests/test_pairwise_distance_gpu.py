@@ -13,7 +13,11 @@ def _col_major(t):
     return t.t().contiguous().t()
 
 
-@pytest.mark.parametrize("metric", ["sqeuclidean", "euclidean", "inner_product", "cosine"])
+# the unexpanded L2 forms have template instances of their own in the tile kernel; the values are those of the expanded forms
+_CDIST = {"l2_unexpanded": "sqeuclidean", "l2_sqrt_unexpanded": "euclidean"}
+
+
+@pytest.mark.parametrize("metric", ["sqeuclidean", "euclidean", "inner_product", "cosine", "l2_unexpanded", "l2_sqrt_unexpanded"])
 @pytest.mark.parametrize("dtype", [np.float32, np.float16])
 @pytest.mark.parametrize("m,n,k", [(300, 200, 33), (1000, 70, 128), (65, 1, 7)])
 def test_row_and_column_major(metric, dtype, m, n, k):
@@ -29,8 +33,10 @@ def test_row_and_column_major(metric, dtype, m, n, k):
     assert row.is_contiguous() and row.shape == (m, n)
     if dtype == np.float32:
         assert (row.cpu().numpy() == oracle.pairwise(x, y, metric=metric)).all()
+    else:  # every fp16 x fp16 product is exact in fp32: the twin on the widened values is the same arithmetic (clamp eps 1e-3)
+        assert (row.cpu().numpy() == oracle.pairwise(x.astype(np.float32), y.astype(np.float32), metric=metric, clamp_eps=1e-3)).all()
     x64, y64 = x.astype(np.float64), y.astype(np.float64)
-    want = x64 @ y64.T if metric == "inner_product" else cdist(x64, y64, metric)
+    want = x64 @ y64.T if metric == "inner_product" else cdist(x64, y64, _CDIST.get(metric, metric))
     assert np.allclose(row.cpu().numpy(), want, rtol=1e-3, atol=2e-3)
     col = pairwise_distance(_col_major(tx), _col_major(ty), metric=metric)
     assert col.shape == (m, n) and col.stride() == (1, m)  # column-major result, like the inputs
