@@ -448,6 +448,9 @@ void train_per_cluster(resources& res, ivf_pq_index& idx, int64_t n_train, const
 
 }  // namespace
 
+// (for the other index types that rotate their rows: ivf_rabitq.hip)
+std::vector<float> random_rotation_matrix(uint32_t rot_dim, uint32_t dim) { return make_rotation_matrix(rot_dim, dim, true); }
+
 void ivf_pq_set_centers(resources& res, ivf_pq_index& idx, const float* centers_flat)
 {
   // centers_flat: device [n_lists, dim]

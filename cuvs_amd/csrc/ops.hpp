@@ -116,6 +116,10 @@ template <typename T>
 void kmeans_predict(resources& res, const T* x, int64_t n, int64_t dim, const float* centers,
                     int n_clusters, uint32_t* labels);
 
+// ---------------------------------------------------------------- ivf_pq_build.hip
+// make_rotation_matrix(rot_dim, dim, force_random = true): the top-left [rot_dim, dim] block of a seeded random orthogonal matrix
+std::vector<float> random_rotation_matrix(uint32_t rot_dim, uint32_t dim);
+
 // ---------------------------------------------------------------- nn_descent.hip
 // kNN graph [n, K] (uint32 ids sorted by distance, self excluded, 0xffffffff = none) by NN-descent; `norms` = canonical
 // |x| per row for the cosine metric (else unused).

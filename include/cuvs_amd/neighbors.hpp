@@ -8,6 +8,7 @@
 #pragma once
 #include <cuvs/core/all.h>
 #include <cuvs_amd/extensions.h>
+#include <cuvs_amd/ivf_rabitq.h>
 
 #include <cstdint>
 #include <memory>
@@ -240,6 +241,57 @@ void search(const resources& res, const search_params& p, const index& idx, devi
   check(cuvsIvfSqSearch(res.get(), cp.p, idx.get(), q.get(), n.get(), d.get(), none), "cuvsIvfSqSearch");
 }
 }  // namespace ivf_sq
+
+namespace ivf_rabitq {
+struct index_params {  // ivf_rabitq.hpp:38-85
+  cuvsDistanceType metric               = L2Expanded;
+  uint32_t n_lists                      = 1024;
+  uint32_t bits_per_dim                 = 3;
+  uint32_t kmeans_n_iters               = 20;
+  uint32_t max_train_points_per_cluster = 256;
+  bool fast_quantize_flag               = true;
+  uint32_t streaming_batch_size         = 100000;
+  bool force_streaming                  = false;
+};
+enum class search_mode { LUT16 = 0, LUT32 = 1, QUANT4 = 2, QUANT8 = 3 };
+struct search_params {
+  uint32_t n_probes = 20;
+  search_mode mode  = search_mode::QUANT4;
+};
+class index {
+ public:
+  index() { check(cuvsAmdIvfRabitqIndexCreate(&h_), "cuvsAmdIvfRabitqIndexCreate"); }
+  ~index() { if (h_) cuvsAmdIvfRabitqIndexDestroy(h_); }
+  index(index&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  index(const index&) = delete;
+  cuvsAmdIvfRabitqIndex_t get() const { return h_; }
+
+ private:
+  cuvsAmdIvfRabitqIndex_t h_ = nullptr;
+};
+// dataset: fp32 rows on the device (make_device_matrix_view) or on the host (make_host_matrix_view)
+inline index build(const resources& res, const index_params& p, device_matrix_view<const float> dataset)
+{
+  detail::c_params<cuvsAmdIvfRabitqIndexParams_t, cuvsAmdIvfRabitqIndexParamsCreate, cuvsAmdIvfRabitqIndexParamsDestroy> cp;
+  *cp.p = cuvsAmdIvfRabitqIndexParams{p.metric, p.n_lists, p.bits_per_dim, p.kmeans_n_iters, p.max_train_points_per_cluster,
+                                      p.fast_quantize_flag, p.streaming_batch_size, p.force_streaming};
+  index idx;
+  detail::tensor<const float> d(dataset);
+  check(cuvsAmdIvfRabitqBuild(res.get(), cp.p, d.get(), idx.get()), "cuvsAmdIvfRabitqBuild");
+  return idx;
+}
+inline void search(const resources& res, const search_params& p, const index& idx, device_matrix_view<const float> queries,
+                   device_matrix_view<int64_t> neighbors, device_matrix_view<float> distances)
+{
+  detail::c_params<cuvsAmdIvfRabitqSearchParams_t, cuvsAmdIvfRabitqSearchParamsCreate, cuvsAmdIvfRabitqSearchParamsDestroy> cp;
+  cp.p->n_probes = p.n_probes;
+  cp.p->mode     = static_cast<cuvsAmdIvfRabitqSearchMode>(p.mode);
+  detail::tensor<const float> q(queries);
+  detail::tensor<int64_t> n(neighbors);
+  detail::tensor<float> d(distances);
+  check(cuvsAmdIvfRabitqSearch(res.get(), cp.p, idx.get(), q.get(), n.get(), d.get()), "cuvsAmdIvfRabitqSearch");
+}
+}  // namespace ivf_rabitq
 
 namespace ivf_pq {
 enum class codebook_gen { PER_SUBSPACE = 0, PER_CLUSTER = 1 };
