@@ -224,6 +224,7 @@ tuning load_tuning_from_env()
   if (const char* e = getenv("CUVS_AMD_NATIVE_FORMAT")) t.native_format = e[0] == '1';
   t.hnsw_pack_rows   = geti("CUVS_AMD_HNSW_PACK_ROWS", 0);
   t.hnsw_pack_host   = geti("CUVS_AMD_HNSW_PACK_HOST", 0);
+  t.eps_slab_rows    = geti("CUVS_AMD_EPS_SLAB_ROWS", 0);
   return t;
 }
 

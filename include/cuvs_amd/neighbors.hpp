@@ -7,6 +7,7 @@
 // cuvsGetLastErrorText(), like the reference's raft::exception.
 #pragma once
 #include <cuvs/core/all.h>
+#include <cuvs_amd/eps_neighbors.h>
 #include <cuvs_amd/extensions.h>
 #include <cuvs_amd/ivf_rabitq.h>
 
@@ -66,6 +67,8 @@ DLDataType dl_dtype()
   else if constexpr (std::is_same_v<U, uint8_t>) return {kDLUInt, 8, 1};
   else if constexpr (std::is_same_v<U, int64_t>) return {kDLInt, 64, 1};
   else if constexpr (std::is_same_v<U, uint32_t>) return {kDLUInt, 32, 1};
+  else if constexpr (std::is_same_v<U, int32_t>) return {kDLInt, 32, 1};
+  else if constexpr (std::is_same_v<U, bool>) return {kDLBool, 8, 1};
   else if constexpr (sizeof(U) == 2) return {kDLFloat, 16, 1};  // __half / _Float16
   else static_assert(sizeof(U) == 0, "unsupported element type");
 }
@@ -86,6 +89,24 @@ struct tensor {
     m.dl_tensor.byte_offset = 0;
   }
   DLManagedTensor* get() { return &m; }
+};
+// a DLManagedTensor describing a device vector of `len` elements
+template <typename T>
+struct vector_tensor {
+  DLManagedTensor m{};
+  int64_t shape[1];
+  vector_tensor(T* p, int64_t len)
+  {
+    shape[0]                = len;
+    m.dl_tensor.data        = const_cast<std::remove_cv_t<T>*>(p);
+    m.dl_tensor.device      = {kDLCUDA, 0};
+    m.dl_tensor.ndim        = 1;
+    m.dl_tensor.dtype       = dl_dtype<T>();
+    m.dl_tensor.shape       = shape;
+    m.dl_tensor.strides     = nullptr;
+    m.dl_tensor.byte_offset = 0;
+  }
+  DLManagedTensor* get() { return m.dl_tensor.data ? &m : nullptr; }  // a null pointer leaves the argument out
 };
 template <typename P, cuvsError_t (*Create)(P*), cuvsError_t (*Destroy)(P)>
 struct c_params {
@@ -515,5 +536,38 @@ void serialize(const resources& res, const std::string& file_prefix, const index
 }
 }  // namespace vamana
 
+namespace epsilon_neighborhood {
+// epsilon_neighborhood.hpp compute(handle, x, y, adj, vd, eps, metric): adj bool [m, n] and vd [m + 1] (IdxT int32_t or
+// int64_t) on the device; a view with a null pointer leaves that output out. eps is the squared radius.
+template <typename T, typename IdxT>
+void compute(const resources& res, device_matrix_view<const T> x, device_matrix_view<const T> y, device_matrix_view<bool> adj,
+             IdxT* vd, float eps, cuvsDistanceType metric = L2Unexpanded)
+{
+  detail::tensor<const T> tx(x), ty(y);
+  detail::tensor<bool> ta(adj);
+  detail::vector_tensor<IdxT> tv(vd, x.extent(0) + 1);
+  check(cuvsAmdEpsNeighbors(res.get(), tx.get(), ty.get(), adj.ptr ? ta.get() : nullptr, tv.get(), eps, metric), "cuvsAmdEpsNeighbors");
+}
+// The CSR forms of ball_cover::eps_nn served by brute force: indptr int64 [m + 1]; indices (int64, `indices_len` entries) and
+// distances (fp32, as long) may be null; vd int64 [m + 1] may be null. max_k == nullptr: the count call (indices null) and the
+// fill call; otherwise one call that keeps the first *max_k ids of a row and returns the largest degree in *max_k.
+template <typename T>
+void csr(const resources& res, device_matrix_view<const T> x, device_matrix_view<const T> y, int64_t* indptr, int64_t* indices,
+         float* distances, int64_t indices_len, int64_t* vd, float eps, int64_t* max_k = nullptr,
+         cuvsDistanceType metric = L2Unexpanded)
+{
+  detail::tensor<const T> tx(x), ty(y);
+  detail::vector_tensor<int64_t> tp(indptr, x.extent(0) + 1), ti(indices, indices_len), tv(vd, x.extent(0) + 1);
+  detail::vector_tensor<float> td(distances, indices_len);
+  check(cuvsAmdEpsNeighborsCsr(res.get(), tx.get(), ty.get(), tp.get(), ti.get(), td.get(), tv.get(), eps, metric, max_k),
+        "cuvsAmdEpsNeighborsCsr");
+}
+}  // namespace epsilon_neighborhood
+
 }  // namespace neighbors
 }  // namespace cuvs
+
+// the extensions (epsilon_neighborhood, ivf_rabitq entry points) are also reachable under the library's own name
+namespace cuvs_amd {
+namespace neighbors = ::cuvs::neighbors;
+}
