@@ -1,5 +1,6 @@
-// Pieces shared by the list-major IVF scans (ivf_pq_search.hip, ivf_flat.hip): work-item construction from the
-// (query, probe) pairs grouped by list, and the register-resident per-wave top-k list.
+// Device-side pieces shared by the list-major IVF scans (ivf_pq_search.hip, ivf_flat.hip, ivf_sq.hip, ivf_rabitq.hip):
+// work-item construction from the (query, probe) pairs grouped by list, and the register-resident per-wave top-k list.
+// The shared host-side steps (coarse search, list assignment, list growth) are in ivf_lists.hpp.
 #pragma once
 #include "ops.hpp"
 #include "device_utils.hpp"

@@ -14,6 +14,7 @@
 // cycles. Per-wave register top lists + shared k-th bounds, two-phase schedule and a per-tile early stop as in
 // the PQ scan. Cosine = dot products + in-kernel row norms. In-list order is ascending source id.
 #include "ivf_common.hpp"
+#include "ivf_lists.hpp"
 #include "ivf_pq_scan3.hpp"
 
 #include <chrono>
@@ -28,24 +29,14 @@
 
 namespace cuvs_amd {
 
-void load_range_as_float(resources& res, const void* data, elem_t et, bool is_host, int64_t dim, int64_t r0,
-                         int64_t cnt, float* out);
-void load_gather_as_float(resources& res, const void* data, elem_t et, bool is_host, int64_t dim,
-                          const uint32_t* d_ids, int64_t cnt, float* out);
-
-struct ivf_flat_index {
+struct ivf_flat_index : ivf_lists {  // data: [padded_rows / 64, n_chunks, 64, 16 bytes] of the element type
   int metric   = 0;
   elem_t dtype = elem_t::f32;
-  uint32_t n_lists = 0, dim = 0;
-  uint32_t veclen = 4, n_chunks = 0;  // elements per 16-byte chunk; chunks per row
-  int64_t size = 0, padded_rows = 0;
+  uint32_t dim = 0;
+  uint32_t veclen = 4;  // elements per 16-byte chunk
   dev_buf<float> centers;       // [n_lists, dim]
   dev_buf<float> center_norms;  // [n_lists] canonical |c|^2
   dev_buf<float> center_norms_sqrt;  // [n_lists] |c| (cosine only: the reference's center_norms for that metric)
-  dev_buf<uint8_t> data;        // [padded_rows / 64, n_chunks, 64, 16 bytes]
-  dev_buf<int64_t> indices;     // [padded_rows]
-  dev_buf<uint32_t> list_sizes, list_offsets;
-  std::vector<uint32_t> h_list_sizes, h_list_offsets;
   mutable flat3_cache scan3;    // fp16 residual copy for the matrix-core tail phase (ivf_pq_scan3.hip), built on first use
 };
 
@@ -110,21 +101,6 @@ __global__ void pack_rows_kernel(pack_args a)
   size_t addr = (((size_t)(fr >> 6) * a.n_chunks + ch) * 64 + (size_t)(fr & 63)) * 16;
   *reinterpret_cast<uint4*>(a.data + addr) = *reinterpret_cast<const uint4*>(tmp);
   if (ch == 0) a.indices[fr] = a.new_ids ? a.new_ids[row] : a.id_base + (int64_t)row;
-}
-
-__global__ void relocate_flat_lists_kernel(const uint8_t* __restrict__ old_data, const int64_t* __restrict__ old_ids,
-                                           const uint32_t* __restrict__ old_off, const uint32_t* __restrict__ old_sizes,
-                                           const uint32_t* __restrict__ new_off, uint32_t n_chunks,
-                                           uint8_t* __restrict__ data, int64_t* __restrict__ ids)
-{
-  const uint32_t L  = blockIdx.x;
-  const uint32_t sz = old_sizes[L];
-  const int64_t so = old_off[L], dn = new_off[L];
-  for (uint32_t i = threadIdx.x; i < sz; i += blockDim.x) ids[dn + i] = old_ids[so + i];
-  const size_t n16 = (size_t)((sz + 63) / 64) * n_chunks * 64;
-  const uint4* s = reinterpret_cast<const uint4*>(old_data + (size_t)(so >> 6) * n_chunks * 1024);
-  uint4* d       = reinterpret_cast<uint4*>(data + (size_t)(dn >> 6) * n_chunks * 1024);
-  for (size_t i = threadIdx.x; i < n16; i += blockDim.x) d[i] = s[i];
 }
 
 struct flat_scan_args {
@@ -660,111 +636,23 @@ void ivf_flat_extend(resources& res, ivf_flat_index& idx, const void* data, elem
   CUVS_EXPECTS(et == idx.dtype, "extend: vector dtype differs from the index dtype");
   CUVS_EXPECTS(new_ids != nullptr || idx.size == 0, "You must pass data indices when the index is non-empty.");
   CUVS_EXPECTS(idx.size + n_new < (int64_t(1) << 32) - 64 * (int64_t)idx.n_lists, "index too large for 32-bit row offsets");
-  const int64_t dim = idx.dim;
-  const size_t esz  = elem_size(et);
-  dev_buf<int64_t> ids_dev;
-  if (new_ids && ids_on_host) {
-    ids_dev = dev_buf<int64_t>(res, n_new);
-    copy_async(res, ids_dev.data(), new_ids, n_new * sizeof(int64_t));
-    new_ids = ids_dev.data();
-  }
-  // labels: predicted with the index metric, like the k-means that trained the centres (ivf_flat_build.cuh:179-200,
-  // :438): L2 argmin; inner product -> the centre with the largest dot product (argmin of |c|^2 - 2 x.c with the |c|^2
-  // term dropped), which is also how the search ranks the probes; cosine -> L2 on unit-length copies
   dev_buf<uint32_t> labels(res, n_new);
-  dev_buf<float> zero_norms(res, idx.metric == M_InnerProduct ? idx.n_lists : 0);
-  if (idx.metric == M_InnerProduct) HIP_TRY(hipMemsetAsync(zero_norms.data(), 0, zero_norms.bytes(), res.stream));
-  const float* label_norms = idx.metric == M_InnerProduct ? zero_norms.data() : idx.center_norms.data();
-  const int64_t batch_rows = std::max<int64_t>(1024, std::min<int64_t>(n_new, (int64_t(1) << 28) / dim));
-  {
-    dev_buf<float> xb(res, (size_t)std::min(batch_rows, n_new) * dim);
-    for (int64_t r0 = 0; r0 < n_new; r0 += batch_rows) {
-      int64_t cnt = std::min(batch_rows, n_new - r0);
-      load_range_as_float(res, data, et, is_host, dim, r0, cnt, xb.data());
-      if (idx.metric == M_CosineExpanded)
-        normalize_rows(res, xb.data(), cnt, dim);  // cosine: rows are assigned to lists on unit-length copies
-      fused_l2_argmin<float>(res, xb.data(), cnt, dim, idx.centers.data(), idx.n_lists, dim, label_norms,
-                             labels.data() + r0, nullptr);
-    }
-  }
-  dev_buf<uint32_t> perm(res, n_new), new_off(res, idx.n_lists + 1);
-  group_by_label(res, labels.data(), n_new, idx.n_lists, perm.data(), new_off.data());
-  std::vector<uint32_t> h_new_off = to_host(res, new_off.data(), idx.n_lists + 1);
-  std::vector<uint32_t> sizes(idx.n_lists), offs(idx.n_lists + 1);
-  int64_t total = 0;
-  for (uint32_t L = 0; L < idx.n_lists; ++L) {
-    sizes[L] = idx.h_list_sizes[L] + (h_new_off[L + 1] - h_new_off[L]);
-    offs[L]  = (uint32_t)total;
-    total += round_up(sizes[L], 64);
-  }
-  offs[idx.n_lists] = (uint32_t)total;
-  auto ndata    = dev_buf<uint8_t>::persistent((size_t)total * idx.n_chunks * 16);
-  auto nindices = dev_buf<int64_t>::persistent((size_t)total);
-  HIP_TRY(hipMemsetAsync(ndata.data(), 0, ndata.bytes(), res.stream));
-  HIP_TRY(hipMemsetAsync(nindices.data(), 0xff, nindices.bytes(), res.stream));
-  dev_buf<uint32_t> d_list_off(res, idx.n_lists + 1);
-  copy_async(res, d_list_off.data(), offs.data(), offs.size() * sizeof(uint32_t));
-  if (idx.size > 0) {
-    hipLaunchKernelGGL(relocate_flat_lists_kernel, dim3(idx.n_lists), dim3(256), 0, res.stream, idx.data.data(),
-                       idx.indices.data(), idx.list_offsets.data(), idx.list_sizes.data(), d_list_off.data(),
-                       idx.n_chunks, ndata.data(), nindices.data());
-  }
-  pack_args a;
-  a.perm = perm.data(); a.labels = labels.data(); a.new_off = new_off.data(); a.old_sizes = idx.list_sizes.data();
-  a.list_off = d_list_off.data(); a.new_ids = new_ids; a.id_base = idx.size;
-  a.dim = idx.dim; a.veclen = idx.veclen; a.n_chunks = idx.n_chunks; a.data = ndata.data(); a.indices = nindices.data();
-  auto launch = [&](const pack_args& pa) {
-    switch (et) {
-      case elem_t::f32: launch_pack<float>(res, pa); break;
-      case elem_t::f16: launch_pack<__half>(res, pa); break;
-      case elem_t::i8: launch_pack<int8_t>(res, pa); break;
-      case elem_t::u8: launch_pack<uint8_t>(res, pa); break;
-    }
-  };
-  const int64_t pb = std::max<int64_t>(64, (int64_t(1) << 22));  // rows per pack launch
-  if (!is_host) {
-    a.src = data; a.src_is_batch = 0;
-    for (int64_t j0 = 0; j0 < n_new; j0 += pb) {
-      a.j0 = j0; a.batch = std::min(pb, n_new - j0);
-      launch(a);
-    }
-  } else {
-    std::vector<uint32_t> h_perm = to_host(res, perm.data(), n_new);
-    const int64_t hb = std::max<int64_t>(1, std::min<int64_t>(n_new, (int64_t(1) << 28) / (dim * (int64_t)esz)));
-    std::vector<char> host((size_t)hb * dim * esz);
-    dev_buf<char> stage(res, host.size());
-    const char* src = static_cast<const char*>(data);
-    for (int64_t j0 = 0; j0 < n_new; j0 += hb) {
-      int64_t cnt = std::min(hb, n_new - j0);
-      for (int64_t i = 0; i < cnt; ++i)
-        memcpy(host.data() + (size_t)i * dim * esz, src + (size_t)h_perm[j0 + i] * dim * esz, dim * esz);
-      copy_async(res, stage.data(), host.data(), (size_t)cnt * dim * esz);
-      a.src = stage.data(); a.src_is_batch = 1; a.j0 = j0; a.batch = cnt;
-      launch(a);
-      sync(res);
-    }
-  }
-  HIP_TRY(hipGetLastError());
-  sync(res);
-  idx.data    = std::move(ndata);
-  idx.indices = std::move(nindices);
-  copy_async(res, idx.list_sizes.data(), sizes.data(), sizes.size() * sizeof(uint32_t));
-  copy_async(res, idx.list_offsets.data(), offs.data(), offs.size() * sizeof(uint32_t));
-  sync(res);
-  idx.h_list_sizes   = sizes;
-  idx.h_list_offsets = offs;
-  idx.size += n_new;
-  idx.padded_rows = total;
-}
-
-static void flat_set_center_norms(resources& res, ivf_flat_index& idx)
-{
-  idx.center_norms = dev_buf<float>::persistent(idx.n_lists);
-  row_norms<float>(res, idx.centers.data(), idx.n_lists, idx.dim, idx.dim, idx.center_norms.data(), false);
-  if (idx.metric == M_CosineExpanded) {
-    idx.center_norms_sqrt = dev_buf<float>::persistent(idx.n_lists);
-    row_norms<float>(res, idx.centers.data(), idx.n_lists, idx.dim, idx.dim, idx.center_norms_sqrt.data(), true);
-  }
+  ivf_assign_lists(res, idx.metric, idx.centers.data(), idx.center_norms.data(), idx.n_lists, idx.dim, data, et, is_host, n_new,
+                   labels.data());
+  ivf_lists_grow(res, idx, labels.data(), data, (size_t)idx.dim * elem_size(et), n_new, is_host, new_ids, ids_on_host,
+                 [&](const ivf_pack_dest& d, int64_t j0, int64_t batch, const void* src, int src_is_batch) {
+                   pack_args a;
+                   a.src = src; a.perm = d.perm; a.labels = d.labels; a.new_off = d.new_off; a.old_sizes = d.old_sizes;
+                   a.list_off = d.list_off; a.new_ids = d.new_ids; a.id_base = d.id_base; a.j0 = j0; a.batch = batch;
+                   a.src_is_batch = src_is_batch; a.dim = idx.dim; a.veclen = idx.veclen; a.n_chunks = idx.n_chunks;
+                   a.data = d.data; a.indices = d.indices;
+                   switch (et) {
+                     case elem_t::f32: launch_pack<float>(res, a); break;
+                     case elem_t::f16: launch_pack<__half>(res, a); break;
+                     case elem_t::i8: launch_pack<int8_t>(res, a); break;
+                     case elem_t::u8: launch_pack<uint8_t>(res, a); break;
+                   }
+                 });
 }
 
 std::unique_ptr<ivf_flat_index> ivf_flat_build(resources& res, const cuvsIvfFlatIndexParams& p, const void* data,
@@ -806,7 +694,7 @@ std::unique_ptr<ivf_flat_index> ivf_flat_build(resources& res, const cuvsIvfFlat
   if (metric == M_CosineExpanded)
     normalize_rows(res, trainset.data(), n_train, dim);
   kmeans_balanced_fit(res, trainset.data(), n_train, dim, (int)p.n_lists, kp, idx->centers.data());
-  flat_set_center_norms(res, *idx);
+  ivf_set_center_norms(res, idx->metric, idx->centers.data(), idx->n_lists, idx->dim, idx->center_norms, idx->center_norms_sqrt);
   trainset.release();
   if (p.add_data_on_build) ivf_flat_extend(res, *idx, data, et, n, is_host, nullptr, false);
   sync(res);
@@ -914,43 +802,9 @@ void ivf_flat_search(resources& res, const ivf_flat_index& idx, uint32_t n_probe
     const int64_t n_pairs = nq * n_probes;
     const char* qptr      = static_cast<const char*>(queries) + (size_t)q0 * idx.dim * esz;
     load_range_as_float(res, queries, et, false, idx.dim, q0, nq, qf.data());
-    // coarse search (ivf_flat_search.cuh:104-187). Common shapes: distances in grouped layout + the best key of every 16-centre
-    // group, selection from the keys and the qualifying groups only (ops.hpp: pairwise_distance_grouped / select_k_grouped,
-    // DESIGN 3.1f) - the values, their order and the tie rule are those of the plain form below
-    bool coarse_done = false;
-    if (res.tune.coarse_grouped != 0 && select_k_grouped_ok(idx.n_lists, (int)n_probes)) {
-      const int64_t ldo = round_up((int64_t)idx.n_lists, 128);
-      dev_buf<float> gdist(res, (size_t)nq * ldo);
-      dev_buf<uint32_t> gkeys(res, (size_t)nq * (ldo / 16));
-      const bool ipm = idx.metric == M_InnerProduct, cosm = idx.metric == M_CosineExpanded;
-      if (!ipm) row_norms<float>(res, qf.data(), nq, idx.dim, idx.dim, qn.data(), cosm);
-      coarse_done = pairwise_distance_grouped(res, qf.data(), nq, idx.dim, idx.centers.data(), idx.n_lists, idx.dim, idx.dim,
-                                              ipm ? nullptr : qn.data(), ipm ? nullptr : (cosm ? idx.center_norms_sqrt.data() : idx.center_norms.data()),
-                                              ipm ? (int)M_InnerProduct : (cosm ? (int)M_CosineExpanded : (int)M_L2Expanded), gdist.data(), ldo,
-                                              gkeys.data(), ldo / 16);
-      if (coarse_done) select_k_grouped(res, gdist.data(), ldo, gkeys.data(), ldo / 16, nq, idx.n_lists, (int)n_probes, pd.data(), probes.data(), !ipm);
-    }
-    if (!coarse_done && dist.data() == nullptr) dist = dev_buf<float>(res, (size_t)bs * idx.n_lists);
-    if (coarse_done) {
-    } else if (idx.metric == M_InnerProduct) {
-      pairwise_distance<float, float>(res, qf.data(), nq, idx.dim, idx.centers.data(), idx.n_lists, idx.dim, idx.dim,
-                                      nullptr, nullptr, M_InnerProduct, dist.data(), idx.n_lists);
-      select_k<uint32_t, uint32_t>(res, dist.data(), nullptr, nq, idx.n_lists, idx.n_lists, (int)n_probes, pd.data(),
-                                   probes.data(), false);
-    } else if (idx.metric == M_CosineExpanded) {
-      // 1 - q.c / (|q| |c|): the same ranking as the reference's -q.c / (|q| |c|) (ivf_flat_search.cuh:130-175)
-      row_norms<float>(res, qf.data(), nq, idx.dim, idx.dim, qn.data(), true);
-      pairwise_distance<float, float>(res, qf.data(), nq, idx.dim, idx.centers.data(), idx.n_lists, idx.dim, idx.dim,
-                                      qn.data(), idx.center_norms_sqrt.data(), M_CosineExpanded, dist.data(), idx.n_lists);
-      select_k<uint32_t, uint32_t>(res, dist.data(), nullptr, nq, idx.n_lists, idx.n_lists, (int)n_probes, pd.data(),
-                                   probes.data(), true);
-    } else {
-      row_norms<float>(res, qf.data(), nq, idx.dim, idx.dim, qn.data(), false);
-      pairwise_distance<float, float>(res, qf.data(), nq, idx.dim, idx.centers.data(), idx.n_lists, idx.dim, idx.dim,
-                                      qn.data(), idx.center_norms.data(), M_L2Expanded, dist.data(), idx.n_lists);
-      select_k<uint32_t, uint32_t>(res, dist.data(), nullptr, nq, idx.n_lists, idx.n_lists, (int)n_probes, pd.data(),
-                                   probes.data(), true);
-    }
+    // coarse search (ivf_flat_search.cuh:104-187)
+    coarse_search(res, idx.centers.data(), idx.dim, idx.n_lists, idx.dim, idx.center_norms.data(), idx.center_norms_sqrt.data(),
+                  idx.metric, qf.data(), nq, n_probes, bs, qn.data(), dist, pd.data(), probes.data());
     trace.mark("coarse search");
     const uint32_t* labels = probes.data();
     if (head > 0) {
@@ -1405,7 +1259,7 @@ std::unique_ptr<ivf_flat_index> flat_read_ref(resources& res, const char* filena
   idx->centers    = r.device_array<float>(res, (int64_t)idx->n_lists * idx->dim);
   if (r.scalar<bool>()) (void)r.host_array<float>(idx->n_lists);
   // canonical |c|^2 (the build's own rounding) rather than the file's
-  flat_set_center_norms(res, *idx);
+  ivf_set_center_norms(res, idx->metric, idx->centers.data(), idx->n_lists, idx->dim, idx->center_norms, idx->center_norms_sqrt);
   idx->h_list_sizes = r.host_array<uint32_t>(idx->n_lists);
   idx->h_list_offsets.assign(idx->n_lists + 1, 0);
   int64_t total = 0, live = 0;

@@ -133,6 +133,9 @@ std::unique_ptr<ivf_pq_index> ivf_pq_build(resources& res, const ivf_pq_build_pa
                                            elem_t et, int64_t n, int64_t dim, bool is_host);
 void ivf_pq_extend(resources& res, ivf_pq_index& idx, const void* data, elem_t et, int64_t n, bool is_host,
                    const int64_t* new_ids, bool ids_on_host);
+// an index without centres, codebooks or rows, and the step that installs its centres ([n_lists, dim] fp32, device)
+std::unique_ptr<ivf_pq_index> ivf_pq_make_empty(resources& res, const ivf_pq_build_params& p, elem_t et, int64_t dim);
+void ivf_pq_set_centers(resources& res, ivf_pq_index& idx, const float* centers_flat);
 // filter_bits: optional bitset over source ids (1 keeps the row; sample_filter.cuh bitset_filter semantics), device memory
 void ivf_pq_search(resources& res, const ivf_pq_search_params& p, const ivf_pq_index& idx, const void* queries,
                    elem_t et, int64_t n_queries, int k, int64_t* neighbors, float* distances,

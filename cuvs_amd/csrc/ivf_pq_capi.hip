@@ -7,11 +7,6 @@
 #include <cuvs/neighbors/ivf_pq.h>
 #include <cuvs_amd/extensions.h>
 
-namespace cuvs_amd {
-std::unique_ptr<ivf_pq_index> ivf_pq_make_empty(resources& res, const ivf_pq_build_params& p, elem_t et, int64_t dim);
-void ivf_pq_set_centers(resources& res, ivf_pq_index& idx, const float* centers_flat);
-}  // namespace cuvs_amd
-
 using namespace cuvs_amd;
 
 namespace {

@@ -27,6 +27,7 @@
 #include "ops.hpp"
 #include "device_utils.hpp"
 #include "ivf_common.hpp"
+#include "ivf_lists.hpp"
 #include "pq_lut_math.hpp"
 #include "ivf_pq_scan3.hpp"
 
@@ -40,9 +41,6 @@
 
 namespace cuvs_amd {
 extern unsigned long long g_pq3_last_stats[6];  // core.hip: cuvsAmdIvfPqLastFilterStats
-
-void load_range_as_float(resources& res, const void* data, elem_t et, bool is_host, int64_t dim, int64_t r0,
-                         int64_t cnt, float* out);
 
 namespace {
 
@@ -1911,36 +1909,10 @@ void select_clusters(resources& res, const ivf_pq_index& idx, const float* qf, i
                                  probes, true);
     return;
   }
-  // fp32 coarse search. Common shapes: the distance tile writes rows in GROUPED layout + the best key of every 16-centre
-  // group, and the selection reads the keys and only the groups that can hold one of the n_probes nearest (ops.hpp:
-  // pairwise_distance_grouped / select_k_grouped) - the values, their order and the tie rule are those of the plain form below
-  if (res.tune.coarse_grouped != 0 && select_k_grouped_ok(idx.n_lists, (int)n_probes)) {
-    const int64_t ldo = round_up((int64_t)idx.n_lists, 128);
-    dev_buf<float> gdist(res, (size_t)nq * ldo);
-    dev_buf<uint32_t> gkeys(res, (size_t)nq * (ldo / 16));
-    dev_buf<float> qn(res, ip ? 0 : nq);
-    if (!ip) row_norms<float>(res, qf, nq, idx.dim, idx.dim, qn.data(), false);
-    if (pairwise_distance_grouped(res, qf, nq, idx.dim, idx.centers.data(), idx.n_lists, idx.dim_ext, idx.dim, ip ? nullptr : qn.data(),
-                                  ip ? nullptr : idx.center_norms.data(), ip ? (int)M_InnerProduct : (int)M_L2Expanded, gdist.data(), ldo,
-                                  gkeys.data(), ldo / 16)) {
-      select_k_grouped(res, gdist.data(), ldo, gkeys.data(), ldo / 16, nq, idx.n_lists, (int)n_probes, pd.data(), probes, !ip);
-      return;
-    }
-  }
-  dev_buf<float> dist(res, (size_t)nq * idx.n_lists);
-  if (ip) {
-    pairwise_distance<float, float>(res, qf, nq, idx.dim, idx.centers.data(), idx.n_lists, idx.dim_ext, idx.dim,
-                                    nullptr, nullptr, M_InnerProduct, dist.data(), idx.n_lists);
-    select_k<uint32_t, uint32_t>(res, dist.data(), nullptr, nq, idx.n_lists, idx.n_lists, (int)n_probes, pd.data(),
-                                 probes, false);
-  } else {
-    dev_buf<float> qn(res, nq);
-    row_norms<float>(res, qf, nq, idx.dim, idx.dim, qn.data(), false);
-    pairwise_distance<float, float>(res, qf, nq, idx.dim, idx.centers.data(), idx.n_lists, idx.dim_ext, idx.dim,
-                                    qn.data(), idx.center_norms.data(), M_L2Expanded, dist.data(), idx.n_lists);
-    select_k<uint32_t, uint32_t>(res, dist.data(), nullptr, nq, idx.n_lists, idx.n_lists, (int)n_probes, pd.data(),
-                                 probes, true);
-  }
+  // fp32 coarse search: centres at pitch dim_ext; cosine ranks unit queries against unit centres by their dot products
+  dev_buf<float> qn(res, ip ? 0 : nq), dist;
+  coarse_search(res, idx.centers.data(), idx.dim_ext, idx.n_lists, idx.dim, idx.center_norms.data(), nullptr,
+                ip ? (int)M_InnerProduct : (int)M_L2Expanded, qf, nq, n_probes, nq, qn.data(), dist, pd.data(), probes);
 }
 
 // rotation of the queries in the coarse type (ivf_pq_search.cuh:995-1017): R rounded like the queries, fp32 output;

@@ -12,6 +12,7 @@
 // expands its 16 bits into the 16 operand bytes of one MFMA K step. Short factors float4 per row, extended codes in the file's
 // bit stream per row, extended factors float2 per row, ids uint32.
 #include "ivf_common.hpp"
+#include "ivf_lists.hpp"
 #include "ivf_rabitq_host.hpp"
 
 #include <cuvs_amd/ivf_rabitq.h>
@@ -19,15 +20,8 @@
 #include <cfloat>
 #include <map>
 #include <mutex>
-#include <numeric>
-#include <random>
 
 namespace cuvs_amd {
-
-void load_range_as_float(resources& res, const void* data, elem_t et, bool is_host, int64_t dim, int64_t r0,
-                         int64_t cnt, float* out);
-void load_gather_as_float(resources& res, const void* data, elem_t et, bool is_host, int64_t dim,
-                          const uint32_t* d_ids, int64_t cnt, float* out);
 
 struct ivf_rabitq_index {
   int metric       = 0;
@@ -657,17 +651,7 @@ std::unique_ptr<ivf_rabitq_index> ivf_rabitq_build(resources& res, const cuvsAmd
   idx->centers = dev_buf<float>::persistent((size_t)p.n_lists * dim);
   {
     const int64_t n_train = std::min<int64_t>(n, (int64_t)p.n_lists * p.max_train_points_per_cluster);
-    std::vector<uint32_t> pick((size_t)n);
-    std::iota(pick.begin(), pick.end(), 0u);
-    if (n_train < n) {
-      std::mt19937_64 rng(137);
-      for (int64_t i = 0; i < n_train; ++i) {
-        const int64_t j = i + (int64_t)(rng() % (uint64_t)(n - i));
-        std::swap(pick[i], pick[j]);
-      }
-      pick.resize((size_t)n_train);
-      std::sort(pick.begin(), pick.end());
-    }
+    const std::vector<uint32_t> pick = pick_train_rows(n, n_train);
     dev_buf<float> trainset(res, (size_t)n_train * dim);
     dev_buf<uint32_t> tids(res, n_train);
     copy_async(res, tids.data(), pick.data(), (size_t)n_train * sizeof(uint32_t));

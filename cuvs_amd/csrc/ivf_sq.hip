@@ -13,38 +13,26 @@
 // (scalar cache -> SGPRs). Per-wave register top lists with shared k-th bounds (k <= 256), or every score written out
 // and selected (k > 256). DESIGN 3.2 has the arithmetic contract.
 #include "ivf_common.hpp"
+#include "ivf_lists.hpp"
 #include "npy_io.hpp"
 
 #include <cuvs/neighbors/ivf_sq.h>
 
 #include <algorithm>
 #include <cfloat>
-#include <numeric>
-#include <random>
 #include <type_traits>
 
 namespace cuvs_amd {
 
-void load_range_as_float(resources& res, const void* data, elem_t et, bool is_host, int64_t dim, int64_t r0,
-                         int64_t cnt, float* out);
-void load_gather_as_float(resources& res, const void* data, elem_t et, bool is_host, int64_t dim,
-                          const uint32_t* d_ids, int64_t cnt, float* out);
-
-struct ivf_sq_index {
+struct ivf_sq_index : ivf_lists {  // data: [padded_rows / 64, n_chunks, 64, 16 codes], the dimension padded to 16
   int metric   = 0;
   elem_t dtype = elem_t::f32;  // element type of the rows the index was built from (f32 / f16)
   bool conservative_memory_allocation = false;
-  uint32_t n_lists = 0, dim = 0;
-  uint32_t n_chunks = 0;  // 16-code chunks per row (dim padded to 16)
-  int64_t size = 0, padded_rows = 0;
+  uint32_t dim = 0;
   dev_buf<float> centers;            // [n_lists, dim]
   dev_buf<float> center_norms;       // [n_lists] canonical |c|^2
   dev_buf<float> center_norms_sqrt;  // [n_lists] |c| (cosine only)
   dev_buf<float> vmin, delta;        // [dim] the scalar quantizer
-  dev_buf<uint8_t> data;             // [padded_rows / 64, n_chunks, 64, 16 codes]
-  dev_buf<int64_t> indices;          // [padded_rows]
-  dev_buf<uint32_t> list_sizes, list_offsets;
-  std::vector<uint32_t> h_list_sizes, h_list_offsets;
 };
 
 namespace {
@@ -163,27 +151,6 @@ __global__ void sq_pack_kernel(sq_pack_args a)
   const size_t addr = (((size_t)(fr >> 6) * a.n_chunks + ch) * 64 + (size_t)(fr & 63)) * 16;
   *reinterpret_cast<uint4*>(a.data + addr) = *reinterpret_cast<const uint4*>(codes);
   if (ch == 0) a.indices[fr] = a.new_ids ? a.new_ids[row] : a.id_base + (int64_t)row;
-}
-
-__global__ void sq_relocate_lists_kernel(const uint8_t* __restrict__ old_data, const int64_t* __restrict__ old_ids,
-                                         const uint32_t* __restrict__ old_off, const uint32_t* __restrict__ old_sizes,
-                                         const uint32_t* __restrict__ new_off, uint32_t n_chunks, uint8_t* __restrict__ data,
-                                         int64_t* __restrict__ ids)
-{
-  const uint32_t L  = blockIdx.x;
-  const uint32_t sz = old_sizes[L];
-  const int64_t so = old_off[L], dn = new_off[L];
-  for (uint32_t i = threadIdx.x; i < sz; i += blockDim.x) ids[dn + i] = old_ids[so + i];
-  const size_t n16 = (size_t)((sz + 63) / 64) * n_chunks * 64;
-  const uint4* s = reinterpret_cast<const uint4*>(old_data + (size_t)(so >> 6) * n_chunks * 1024);
-  uint4* dd      = reinterpret_cast<uint4*>(data + (size_t)(dn >> 6) * n_chunks * 1024);
-  for (size_t i = threadIdx.x; i < n16; i += blockDim.x) dd[i] = s[i];
-}
-
-__global__ void sq_zero_norms_kernel(float* p, int n)
-{
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = 0.f;
 }
 
 // ------------------------------------------------------------------ search
@@ -574,25 +541,6 @@ void launch_sq_scan(resources& res, const sq_scan_args& a, int metric_kind, size
   HIP_TRY(hipGetLastError());
 }
 
-// list labels of fp32 rows with the index metric (the rule of ivf_flat_extend): L2 argmin; inner product: the largest dot
-// product (|c|^2 term dropped); cosine: L2 on unit-length copies (x is normalised in place)
-void sq_predict(resources& res, const ivf_sq_index& idx, float* x, int64_t cnt, const float* zero_norms, uint32_t* labels)
-{
-  if (idx.metric == M_CosineExpanded) normalize_rows(res, x, cnt, idx.dim);
-  const float* norms = idx.metric == M_InnerProduct ? zero_norms : idx.center_norms.data();
-  fused_l2_argmin<float>(res, x, cnt, idx.dim, idx.centers.data(), idx.n_lists, idx.dim, norms, labels, nullptr);
-}
-
-void sq_set_center_norms(resources& res, ivf_sq_index& idx)
-{
-  idx.center_norms = dev_buf<float>::persistent(idx.n_lists);
-  row_norms<float>(res, idx.centers.data(), idx.n_lists, idx.dim, idx.dim, idx.center_norms.data(), false);
-  if (idx.metric == M_CosineExpanded) {
-    idx.center_norms_sqrt = dev_buf<float>::persistent(idx.n_lists);
-    row_norms<float>(res, idx.centers.data(), idx.n_lists, idx.dim, idx.dim, idx.center_norms_sqrt.data(), true);
-  }
-}
-
 std::unique_ptr<ivf_sq_index> sq_empty_index(resources& res, int metric, uint32_t n_lists, uint32_t dim, bool cma)
 {
   auto idx      = std::make_unique<ivf_sq_index>();
@@ -622,93 +570,22 @@ void ivf_sq_extend(resources& res, ivf_sq_index& idx, const void* data, elem_t e
   CUVS_EXPECTS(et == elem_t::f32 || et == elem_t::f16, "ivf_sq::extend: vectors must be float32 or float16");
   CUVS_EXPECTS(new_ids != nullptr || idx.size == 0, "You must pass data indices when the index is non-empty.");
   CUVS_EXPECTS(idx.size + n_new < (int64_t(1) << 32) - 64 * (int64_t)idx.n_lists, "index too large for 32-bit row offsets");
-  const int64_t dim = idx.dim;
-  const size_t esz  = elem_size(et);
-  dev_buf<int64_t> ids_dev;
-  if (new_ids && ids_on_host) {
-    ids_dev = dev_buf<int64_t>(res, n_new);
-    copy_async(res, ids_dev.data(), new_ids, n_new * sizeof(int64_t));
-    new_ids = ids_dev.data();
-  }
   dev_buf<uint32_t> labels(res, n_new);
-  dev_buf<float> zero_norms(res, idx.n_lists);
-  hipLaunchKernelGGL(sq_zero_norms_kernel, dim3(grid_blocks(idx.n_lists, 256)), dim3(256), 0, res.stream, zero_norms.data(),
-                     (int)idx.n_lists);
-  const int64_t batch_rows = std::max<int64_t>(1024, std::min<int64_t>(n_new, (int64_t(1) << 28) / dim));
-  {
-    dev_buf<float> xb(res, (size_t)std::min(batch_rows, n_new) * dim);
-    for (int64_t r0 = 0; r0 < n_new; r0 += batch_rows) {
-      const int64_t cnt = std::min(batch_rows, n_new - r0);
-      load_range_as_float(res, data, et, is_host, dim, r0, cnt, xb.data());
-      sq_predict(res, idx, xb.data(), cnt, zero_norms.data(), labels.data() + r0);
-    }
-  }
-  // rows appended to their lists in input order: perm = rows ordered by (label, row)
-  dev_buf<uint32_t> perm(res, n_new), new_off(res, idx.n_lists + 1);
-  group_by_label(res, labels.data(), n_new, idx.n_lists, perm.data(), new_off.data());
-  std::vector<uint32_t> h_new_off = to_host(res, new_off.data(), idx.n_lists + 1);
-  std::vector<uint32_t> sizes(idx.n_lists), offs(idx.n_lists + 1);
-  int64_t total = 0;
-  for (uint32_t L = 0; L < idx.n_lists; ++L) {
-    sizes[L] = idx.h_list_sizes[L] + (h_new_off[L + 1] - h_new_off[L]);
-    offs[L]  = (uint32_t)total;
-    total += round_up(sizes[L], 64);
-  }
-  offs[idx.n_lists] = (uint32_t)total;
-  auto ndata    = dev_buf<uint8_t>::persistent((size_t)total * idx.n_chunks * 16);
-  auto nindices = dev_buf<int64_t>::persistent((size_t)total);
-  HIP_TRY(hipMemsetAsync(ndata.data(), 0, ndata.bytes(), res.stream));
-  HIP_TRY(hipMemsetAsync(nindices.data(), 0xff, nindices.bytes(), res.stream));
-  dev_buf<uint32_t> d_list_off(res, idx.n_lists + 1);
-  copy_async(res, d_list_off.data(), offs.data(), offs.size() * sizeof(uint32_t));
-  if (idx.size > 0)
-    hipLaunchKernelGGL(sq_relocate_lists_kernel, dim3(idx.n_lists), dim3(256), 0, res.stream, idx.data.data(), idx.indices.data(),
-                       idx.list_offsets.data(), idx.list_sizes.data(), d_list_off.data(), idx.n_chunks, ndata.data(), nindices.data());
-  sq_pack_args a;
-  a.perm = perm.data(); a.labels = labels.data(); a.new_off = new_off.data(); a.old_sizes = idx.list_sizes.data();
-  a.list_off = d_list_off.data(); a.new_ids = new_ids; a.id_base = idx.size;
-  a.centers = idx.centers.data(); a.vmin = idx.vmin.data(); a.delta = idx.delta.data();
-  a.dim = idx.dim; a.n_chunks = idx.n_chunks; a.data = ndata.data(); a.indices = nindices.data();
-  auto launch = [&](const sq_pack_args& pa) {
-    const int64_t work = pa.batch * pa.n_chunks;
-    if (et == elem_t::f32) hipLaunchKernelGGL(sq_pack_kernel<float>, dim3(grid_blocks(work, 256)), dim3(256), 0, res.stream, pa);
-    else                   hipLaunchKernelGGL(sq_pack_kernel<__half>, dim3(grid_blocks(work, 256)), dim3(256), 0, res.stream, pa);
-  };
-  const int64_t pb = int64_t(1) << 22;  // rows per pack launch
-  if (!is_host) {
-    a.src = data; a.src_is_batch = 0;
-    for (int64_t j0 = 0; j0 < n_new; j0 += pb) {
-      a.j0 = j0; a.batch = std::min(pb, n_new - j0);
-      launch(a);
-    }
-  } else {
-    std::vector<uint32_t> h_perm = to_host(res, perm.data(), n_new);
-    const int64_t hb = std::max<int64_t>(1, std::min<int64_t>(n_new, (int64_t(1) << 28) / (dim * (int64_t)esz)));
-    std::vector<char> host((size_t)hb * dim * esz);
-    dev_buf<char> stage(res, host.size());
-    const char* src = static_cast<const char*>(data);
-    for (int64_t j0 = 0; j0 < n_new; j0 += hb) {
-      const int64_t cnt = std::min(hb, n_new - j0);
-      for (int64_t i = 0; i < cnt; ++i)
-        memcpy(host.data() + (size_t)i * dim * esz, src + (size_t)h_perm[j0 + i] * dim * esz, dim * esz);
-      copy_async(res, stage.data(), host.data(), (size_t)cnt * dim * esz);
-      a.src = stage.data(); a.src_is_batch = 1; a.j0 = j0; a.batch = cnt;
-      launch(a);
-      sync(res);
-    }
-  }
-  HIP_TRY(hipGetLastError());
+  ivf_assign_lists(res, idx.metric, idx.centers.data(), idx.center_norms.data(), idx.n_lists, idx.dim, data, et, is_host, n_new,
+                   labels.data());
+  ivf_lists_grow(res, idx, labels.data(), data, (size_t)idx.dim * elem_size(et), n_new, is_host, new_ids, ids_on_host,
+                 [&](const ivf_pack_dest& d, int64_t j0, int64_t batch, const void* src, int src_is_batch) {
+                   sq_pack_args a;
+                   a.src = src; a.perm = d.perm; a.labels = d.labels; a.new_off = d.new_off; a.old_sizes = d.old_sizes;
+                   a.list_off = d.list_off; a.new_ids = d.new_ids; a.id_base = d.id_base; a.j0 = j0; a.batch = batch;
+                   a.src_is_batch = src_is_batch; a.centers = idx.centers.data(); a.vmin = idx.vmin.data();
+                   a.delta = idx.delta.data(); a.dim = idx.dim; a.n_chunks = idx.n_chunks; a.data = d.data; a.indices = d.indices;
+                   const int64_t work = batch * idx.n_chunks;
+                   if (et == elem_t::f32) hipLaunchKernelGGL(sq_pack_kernel<float>, dim3(grid_blocks(work, 256)), dim3(256), 0, res.stream, a);
+                   else                   hipLaunchKernelGGL(sq_pack_kernel<__half>, dim3(grid_blocks(work, 256)), dim3(256), 0, res.stream, a);
+                 });
+  ivf_set_center_norms(res, idx.metric, idx.centers.data(), idx.n_lists, idx.dim, idx.center_norms, idx.center_norms_sqrt);
   sync(res);
-  idx.data    = std::move(ndata);
-  idx.indices = std::move(nindices);
-  copy_async(res, idx.list_sizes.data(), sizes.data(), sizes.size() * sizeof(uint32_t));
-  copy_async(res, idx.list_offsets.data(), offs.data(), offs.size() * sizeof(uint32_t));
-  sq_set_center_norms(res, idx);
-  sync(res);
-  idx.h_list_sizes   = sizes;
-  idx.h_list_offsets = offs;
-  idx.size += n_new;
-  idx.padded_rows = total;
 }
 
 std::unique_ptr<ivf_sq_index> ivf_sq_build(resources& res, const cuvsIvfSqIndexParams& p, const void* data, elem_t et,
@@ -728,17 +605,7 @@ std::unique_ptr<ivf_sq_index> ivf_sq_build(resources& res, const cuvsIvfSqIndexP
   // training sample: min(n, n_lists * max_train_points_per_cluster) distinct rows, chosen by a seeded shuffle (all rows
   // when the dataset is no larger), gathered in ascending row order
   const int64_t n_train = std::min<int64_t>(n, (int64_t)p.n_lists * p.max_train_points_per_cluster);
-  std::vector<uint32_t> pick((size_t)n);
-  std::iota(pick.begin(), pick.end(), 0u);
-  if (n_train < n) {
-    std::mt19937_64 rng(137);
-    for (int64_t i = 0; i < n_train; ++i) {
-      const int64_t j = i + (int64_t)(rng() % (uint64_t)(n - i));
-      std::swap(pick[i], pick[j]);
-    }
-    pick.resize((size_t)n_train);
-    std::sort(pick.begin(), pick.end());
-  }
+  const std::vector<uint32_t> pick = pick_train_rows(n, n_train);
   dev_buf<float> trainset(res, (size_t)n_train * dim);
   {
     dev_buf<uint32_t> ids(res, n_train);
@@ -755,13 +622,11 @@ std::unique_ptr<ivf_sq_index> ivf_sq_build(resources& res, const cuvsIvfSqIndexP
     kp.n_iters       = (int)p.kmeans_n_iters;
     kp.inner_product = metric == M_InnerProduct;
     kmeans_balanced_fit(res, fit.data(), n_train, dim, (int)p.n_lists, kp, idx->centers.data());
-    sq_set_center_norms(res, *idx);
+    ivf_set_center_norms(res, metric, idx->centers.data(), idx->n_lists, idx->dim, idx->center_norms, idx->center_norms_sqrt);
     HIP_TRY(hipMemcpyAsync(fit.data(), trainset.data(), trainset.bytes(), hipMemcpyDeviceToDevice, res.stream));
     dev_buf<uint32_t> labels(res, n_train);
-    dev_buf<float> zero_norms(res, p.n_lists);
-    hipLaunchKernelGGL(sq_zero_norms_kernel, dim3(grid_blocks(p.n_lists, 256)), dim3(256), 0, res.stream, zero_norms.data(),
-                       (int)p.n_lists);
-    sq_predict(res, *idx, fit.data(), n_train, zero_norms.data(), labels.data());
+    ivf_assign_lists(res, metric, idx->centers.data(), idx->center_norms.data(), idx->n_lists, idx->dim, fit.data(), n_train,
+                     labels.data());
     // residuals -> per-dimension range -> quantizer
     hipLaunchKernelGGL(sq_residuals_kernel, dim3(grid_blocks(n_train * dim, 256)), dim3(256), 0, res.stream, trainset.data(),
                        idx->centers.data(), labels.data(), n_train, (uint32_t)dim, et == elem_t::f16 ? 1 : 0);
@@ -793,7 +658,7 @@ void ivf_sq_search(resources& res, const ivf_sq_index& idx, uint32_t n_probes_in
   const int k_scan        = large_k ? 1 : k;
   const uint32_t dim_pad  = idx.n_chunks * 16;
   const int metric_kind   = idx.metric == M_InnerProduct ? 1 : idx.metric == M_CosineExpanded ? 2 : 0;
-  const bool ipm = idx.metric == M_InnerProduct, cosm = idx.metric == M_CosineExpanded;
+  const bool cosm = idx.metric == M_CosineExpanded;
   const size_t smem      = ((((size_t)qpb * kSqWaves * k_scan * 8) + 15) & ~size_t(15)) + 2 * 16 * 4;
   const size_t scores_ld = large_k ? largest_lists_total(idx.h_list_sizes, n_probes) : 0;
   int64_t max_batch = 1 << 15;
@@ -829,40 +694,8 @@ void ivf_sq_search(resources& res, const ivf_sq_index& idx, uint32_t n_probes_in
     const int64_t n_pairs = nq * n_probes;
     load_range_as_float(res, queries, et, false, idx.dim, q0, nq, qf.data());
     (void)esz;
-    // coarse search: the calls and tie rule of ivf_flat_search
-    bool coarse_done = false;
-    if (res.tune.coarse_grouped != 0 && select_k_grouped_ok(idx.n_lists, (int)n_probes)) {
-      const int64_t ldo = round_up((int64_t)idx.n_lists, 128);
-      dev_buf<float> gdist(res, (size_t)nq * ldo);
-      dev_buf<uint32_t> gkeys(res, (size_t)nq * (ldo / 16));
-      if (!ipm) row_norms<float>(res, qf.data(), nq, idx.dim, idx.dim, qn.data(), cosm);
-      coarse_done = pairwise_distance_grouped(res, qf.data(), nq, idx.dim, idx.centers.data(), idx.n_lists, idx.dim, idx.dim,
-                                              ipm ? nullptr : qn.data(), ipm ? nullptr : (cosm ? idx.center_norms_sqrt.data() : idx.center_norms.data()),
-                                              ipm ? (int)M_InnerProduct : (cosm ? (int)M_CosineExpanded : (int)M_L2Expanded), gdist.data(), ldo,
-                                              gkeys.data(), ldo / 16);
-      if (coarse_done)
-        select_k_grouped(res, gdist.data(), ldo, gkeys.data(), ldo / 16, nq, idx.n_lists, (int)n_probes, pd.data(), probes.data(), !ipm);
-    }
-    if (!coarse_done && dist.data() == nullptr) dist = dev_buf<float>(res, (size_t)bs * idx.n_lists);
-    if (coarse_done) {
-    } else if (ipm) {
-      pairwise_distance<float, float>(res, qf.data(), nq, idx.dim, idx.centers.data(), idx.n_lists, idx.dim, idx.dim, nullptr,
-                                      nullptr, M_InnerProduct, dist.data(), idx.n_lists);
-      select_k<uint32_t, uint32_t>(res, dist.data(), nullptr, nq, idx.n_lists, idx.n_lists, (int)n_probes, pd.data(),
-                                   probes.data(), false);
-    } else if (cosm) {
-      row_norms<float>(res, qf.data(), nq, idx.dim, idx.dim, qn.data(), true);
-      pairwise_distance<float, float>(res, qf.data(), nq, idx.dim, idx.centers.data(), idx.n_lists, idx.dim, idx.dim, qn.data(),
-                                      idx.center_norms_sqrt.data(), M_CosineExpanded, dist.data(), idx.n_lists);
-      select_k<uint32_t, uint32_t>(res, dist.data(), nullptr, nq, idx.n_lists, idx.n_lists, (int)n_probes, pd.data(),
-                                   probes.data(), true);
-    } else {
-      row_norms<float>(res, qf.data(), nq, idx.dim, idx.dim, qn.data(), false);
-      pairwise_distance<float, float>(res, qf.data(), nq, idx.dim, idx.centers.data(), idx.n_lists, idx.dim, idx.dim, qn.data(),
-                                      idx.center_norms.data(), M_L2Expanded, dist.data(), idx.n_lists);
-      select_k<uint32_t, uint32_t>(res, dist.data(), nullptr, nq, idx.n_lists, idx.n_lists, (int)n_probes, pd.data(),
-                                   probes.data(), true);
-    }
+    coarse_search(res, idx.centers.data(), idx.dim, idx.n_lists, idx.dim, idx.center_norms.data(), idx.center_norms_sqrt.data(),
+                  idx.metric, qf.data(), nq, n_probes, bs, qn.data(), dist, pd.data(), probes.data());
     const uint32_t* labels = probes.data();
     if (head > 0) {
       hipLaunchKernelGGL(phase_labels_kernel, dim3(grid_blocks(n_pairs, 256)), dim3(256), 0, res.stream, probes.data(), n_pairs,
@@ -1143,7 +976,8 @@ std::unique_ptr<ivf_sq_index> sq_read_ref(resources& res, const char* filename)
   idx->size = size;
   idx->centers = r.device_array<float>(res, (int64_t)n_lists * dim);
   if (r.scalar<bool>()) (void)r.host_array<float>(n_lists);
-  sq_set_center_norms(res, *idx);  // canonical norms (the build's own rounding) rather than the file's
+  // canonical norms (the build's own rounding) rather than the file's
+  ivf_set_center_norms(res, idx->metric, idx->centers.data(), idx->n_lists, idx->dim, idx->center_norms, idx->center_norms_sqrt);
   idx->vmin  = r.device_array<float>(res, dim);
   idx->delta = r.device_array<float>(res, dim);
   idx->h_list_sizes = r.host_array<uint32_t>(n_lists);

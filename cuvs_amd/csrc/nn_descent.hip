@@ -22,11 +22,6 @@
 
 namespace cuvs_amd {
 
-void load_range_as_float(resources& res, const void* data, elem_t et, bool is_host, int64_t dim, int64_t r0,
-                         int64_t cnt, float* out);
-void load_gather_as_float(resources& res, const void* data, elem_t et, bool is_host, int64_t dim,
-                          const uint32_t* d_ids, int64_t cnt, float* out);
-
 namespace {
 
 constexpr uint32_t kNew     = 0x80000000u;

@@ -119,6 +119,12 @@ void kmeans_predict(resources& res, const T* x, int64_t n, int64_t dim, const fl
 // ---------------------------------------------------------------- ivf_pq_build.hip
 // make_rotation_matrix(rot_dim, dim, force_random = true): the top-left [rot_dim, dim] block of a seeded random orthogonal matrix
 std::vector<float> random_rotation_matrix(uint32_t rot_dim, uint32_t dim);
+// rows of any element type, host or device, as fp32 [cnt, dim] on the device (int8 / uint8: mapped by 1 / 128, 1 / 256):
+// rows [r0, r0 + cnt), or rows d_ids[0 .. cnt) (device ids)
+void load_range_as_float(resources& res, const void* data, elem_t et, bool is_host, int64_t dim, int64_t r0,
+                         int64_t cnt, float* out);
+void load_gather_as_float(resources& res, const void* data, elem_t et, bool is_host, int64_t dim,
+                          const uint32_t* d_ids, int64_t cnt, float* out);
 
 // ---------------------------------------------------------------- nn_descent.hip
 // kNN graph [n, K] (uint32 ids sorted by distance, self excluded, 0xffffffff = none) by NN-descent; `norms` = canonical

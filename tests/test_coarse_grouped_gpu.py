@@ -154,3 +154,28 @@ def test_ivf_flat_search_same_with_and_without_the_grouped_coarse_search(metric,
     d1, i1 = ivf_flat.search(sp, index, qt, 10, resources=r1)
     r1.sync()
     assert torch.equal(i0, i1) and torch.equal(d0, d1)
+
+
+@pytest.mark.parametrize("metric", ["sqeuclidean", "inner_product", "cosine"])
+def test_ivf_sq_search_same_with_and_without_the_grouped_coarse_search(metric, monkeypatch):
+    """cuvsIvfSqSearch at n_lists 4096 (the smallest count the grouped selection takes): the default handle (grouped coarse
+    search) against CUVS_AMD_COARSE_GROUPED=0."""
+    import torch
+    import cuvs_amd
+    from cuvs_amd.neighbors import ivf_sq
+
+    rng = np.random.default_rng(4)
+    x = rng.standard_normal((50000, 32)).astype(np.float32)
+    q = rng.standard_normal((400, 32)).astype(np.float32)
+    xt, qt = torch.from_numpy(x).cuda(), torch.from_numpy(q).cuda()
+    r0 = cuvs_amd.common.Resources()
+    index = ivf_sq.build(ivf_sq.IndexParams(n_lists=4096, kmeans_n_iters=4, metric=metric), xt, resources=r0)
+    sp = ivf_sq.SearchParams(n_probes=48)
+    d0, i0 = ivf_sq.search(sp, index, qt, 10, resources=r0)
+    r0.sync()
+    monkeypatch.setenv("CUVS_AMD_COARSE_GROUPED", "0")
+    r1 = cuvs_amd.common.Resources()
+    monkeypatch.delenv("CUVS_AMD_COARSE_GROUPED")
+    d1, i1 = ivf_sq.search(sp, index, qt, 10, resources=r1)
+    r1.sync()
+    assert torch.equal(i0, i1) and torch.equal(d0, d1)

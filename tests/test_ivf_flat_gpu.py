@@ -134,6 +134,40 @@ def test_extend():
     assert np.array_equal(np.sort(np.concatenate(ex["ids"])), np.arange(5000))
 
 
+@pytest.mark.parametrize("dtype", [np.float32, np.int8])
+def test_extend_halves_give_the_lists_file_and_results_of_one_build(dtype, tmp_path):
+    """One build over all rows (A), an empty index extended twice by halves from device tensors (B) and from host rows
+    with host ids (C): the same lists, the same file byte for byte, the same search results bit for bit. dim 20 leaves a
+    padded last chunk for both types (4 and 16 elements per chunk), list sizes are no multiples of 64 and the second
+    extend moves every list."""
+    import torch
+    from cuvs_amd.neighbors import ivf_flat
+
+    x, q = _gen(5000, 20, 80, seed=6, dtype=dtype)
+    xt = torch.from_numpy(x).cuda()
+    a = _build(x, n_lists=16)
+    b = _build(x, n_lists=16, add_data_on_build=False)
+    c = _build(x, n_lists=16, add_data_on_build=False)
+    assert ivf_flat.export_for_oracle(b, dtype)["list_sizes"].sum() == 0
+    for lo, hi in ((0, 2500), (2500, 5000)):
+        ivf_flat.extend(b, xt[lo:hi], torch.arange(lo, hi, dtype=torch.int64, device="cuda"))
+        ivf_flat.extend(c, x[lo:hi], np.arange(lo, hi, dtype=np.int64))
+    ea = ivf_flat.export_for_oracle(a, dtype)
+    assert (ea["list_sizes"] % 64 != 0).any() and ea["list_sizes"].sum() == 5000
+    da, ia = _search(a, q, 10, 5)
+    ivf_flat.save(str(tmp_path / "a.bin"), a)
+    file_a = open(tmp_path / "a.bin", "rb").read()
+    for name, other in (("b", b), ("c", c)):
+        eo = ivf_flat.export_for_oracle(other, dtype)
+        assert np.array_equal(ea["list_sizes"], eo["list_sizes"]), name
+        for L in range(16):
+            assert np.array_equal(ea["ids"][L], eo["ids"][L]) and np.array_equal(ea["rows"][L], eo["rows"][L]), (name, L)
+        ivf_flat.save(str(tmp_path / f"{name}.bin"), other)
+        assert open(tmp_path / f"{name}.bin", "rb").read() == file_a, name
+        do, io = _search(other, q, 10, 5)
+        assert np.array_equal(ia, io) and np.array_equal(da.view(np.uint32), do.view(np.uint32)), name
+
+
 def test_host_dataset_build():
     from cuvs_amd.neighbors import ivf_flat
 
