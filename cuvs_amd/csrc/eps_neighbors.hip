@@ -12,6 +12,7 @@
 // Epilogues: dense (adjacency bytes as 16-byte stores, degrees by integer atomics) and count (bit mask + per-tile counts in
 // workspace, no atomics). eps_fill_kernel writes a row's ids in ascending order from the mask.
 #include "common.hpp"
+#include "dl_desc.hpp"
 #include "eps_neighbors_host.hpp"
 
 #include <cuvs_amd/eps_neighbors.h>
@@ -300,24 +301,6 @@ __global__ __launch_bounds__(kThreads) void eps_fill_kernel(const T* __restrict_
 }
 
 // ---------------------------------------------------------------- host side
-H::tensor_desc desc_of(const DLManagedTensor* t)
-{
-  H::tensor_desc d;
-  if (t == nullptr) return d;
-  const DLTensor& s = t->dl_tensor;
-  d.present    = true;
-  d.ndim       = s.ndim;
-  for (int i = 0; i < 2 && i < s.ndim; ++i) d.shape[i] = s.shape[i];
-  bool empty = false;
-  for (int i = 0; i < s.ndim; ++i) empty = empty || s.shape[i] == 0;
-  d.contiguous = empty || is_c_contiguous(s);  // (no element: the strides say nothing)
-  d.on_device  = is_device_accessible(s);
-  d.code       = s.dtype.code;
-  d.bits       = s.dtype.bits;
-  d.lanes      = s.dtype.lanes;
-  return d;
-}
-
 struct eps_rows {
   const void* x;
   const void* y;

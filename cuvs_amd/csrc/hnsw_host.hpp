@@ -21,6 +21,8 @@
 //   heuristic : candidates ascending; one is kept unless a kept one is strictly nearer to it than the base is
 //   entry     : a row whose level is at least the top level becomes the entry point (the largest id on the top level)
 #pragma once
+#include "mix_hash.hpp"
+
 #include <algorithm>
 #include <atomic>
 #include <cfloat>
@@ -70,15 +72,8 @@ inline void hfail(const char* fmt, ...)
 }
 
 // ---------------------------------------------------------------- levels
-// (the finalizer of MurmurHash3 over i + seed * golden ratio)
-CUVS_AMD_HNSW_HD inline uint32_t level_hash(uint32_t seed, uint32_t i)
-{
-  uint32_t x = i + seed * 0x9E3779B9u;
-  x ^= x >> 16; x *= 0x85EBCA6Bu;
-  x ^= x >> 13; x *= 0xC2B2AE35u;
-  x ^= x >> 16;
-  return x;
-}
+// (the finalizer of MurmurHash3 over i + seed * golden ratio: mix_hash.hpp, shared with the ball cover's landmark draw)
+CUVS_AMD_HNSW_HD inline uint32_t level_hash(uint32_t seed, uint32_t i) { return mix_hash(seed, i); }
 struct level_rule {
   uint32_t t[kMaxLevels];  // T_1 .. T_count, strictly decreasing, all > 0
   int count;

@@ -30,6 +30,16 @@ def make_filter(prefilter):
     return cuvsFilter(t.addr, ftype), t
 
 
+def optional_tensor(t):
+    """DLPack view of an optional tensor (bool adjacency goes as bytes); (None, NULL) when absent"""
+    if t is None:
+        return None, None
+    if isinstance(t, torch.Tensor) and t.dtype == torch.bool:
+        t = t.view(torch.uint8)
+    w = Tensor(t)
+    return w, w.ptr
+
+
 def out_buffers(m, k, neighbors, distances, idx_dtype=torch.int64):
     if neighbors is None:
         neighbors = torch.empty((m, k), dtype=idx_dtype, device="cuda")

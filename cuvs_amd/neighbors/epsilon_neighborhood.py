@@ -12,20 +12,11 @@ import torch
 from .._lib import Tensor, check, lib
 from ..common import auto_sync_resources
 from ..distance import DISTANCE_TYPES
+from ._util import optional_tensor as _t
 
 
 def _metric(metric):
     return DISTANCE_TYPES[metric] if isinstance(metric, str) else int(metric)
-
-
-def _t(t):
-    """DLPack view of an optional tensor (bool adjacency goes as bytes); (None, NULL) when absent"""
-    if t is None:
-        return None, None
-    if isinstance(t, torch.Tensor) and t.dtype == torch.bool:
-        t = t.view(torch.uint8)
-    w = Tensor(t)
-    return w, w.ptr
 
 
 @auto_sync_resources

@@ -7,10 +7,12 @@
 // cuvsGetLastErrorText(), like the reference's raft::exception.
 #pragma once
 #include <cuvs/core/all.h>
+#include <cuvs_amd/ball_cover.h>
 #include <cuvs_amd/eps_neighbors.h>
 #include <cuvs_amd/extensions.h>
 #include <cuvs_amd/ivf_rabitq.h>
 
+#include <array>
 #include <cstdint>
 #include <memory>
 #include <stdexcept>
@@ -564,10 +566,99 @@ void csr(const resources& res, device_matrix_view<const T> x, device_matrix_view
 }
 }  // namespace epsilon_neighborhood
 
+namespace ball_cover {
+// ball_cover.hpp: a landmark index over 2-D / 3-D fp32 rows (eps_nn: up to 32 columns), exact k-NN and eps_nn through it.
+// Unlike the reference's index, this one owns a reordered copy of the rows: the dataset need not outlive build().
+struct index_params {
+  cuvsDistanceType metric = L2SqrtExpanded;  // L2SqrtExpanded, L2SqrtUnexpanded or Haversine
+  uint32_t n_landmarks    = 0;               // 0: floor(sqrt(m))
+  uint32_t seed           = 0;
+};
+class index {
+ public:
+  index() { check(cuvsAmdBallCoverIndexCreate(&h_), "cuvsAmdBallCoverIndexCreate"); }
+  ~index() { if (h_) cuvsAmdBallCoverIndexDestroy(h_); }
+  index(index&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  index(const index&) = delete;
+  cuvsAmdBallCoverIndex_t get() const { return h_; }
+  int64_t n_landmarks() const { int64_t v = 0; check(cuvsAmdBallCoverIndexGetNLandmarks(h_, &v), "cuvsAmdBallCoverIndexGetNLandmarks"); return v; }
+  int64_t size() const { int64_t v = 0; check(cuvsAmdBallCoverIndexGetSize(h_, &v), "cuvsAmdBallCoverIndexGetSize"); return v; }
+  int64_t dim() const { int64_t v = 0; check(cuvsAmdBallCoverIndexGetDim(h_, &v), "cuvsAmdBallCoverIndexGetDim"); return v; }
+  cuvsDistanceType metric() const
+  {
+    cuvsDistanceType v = L2SqrtExpanded;
+    check(cuvsAmdBallCoverIndexGetMetric(h_, &v), "cuvsAmdBallCoverIndexGetMetric");
+    return v;
+  }
+
+ private:
+  cuvsAmdBallCoverIndex_t h_ = nullptr;
+};
+using c_index_params = detail::c_params<cuvsAmdBallCoverIndexParams_t, cuvsAmdBallCoverIndexParamsCreate, cuvsAmdBallCoverIndexParamsDestroy>;
+inline index build(const resources& res, const index_params& p, device_matrix_view<const float> dataset)
+{
+  c_index_params cp;
+  *cp.p = cuvsAmdBallCoverIndexParams{p.metric, p.n_landmarks, p.seed};
+  index idx;
+  detail::tensor<const float> d(dataset);
+  check(cuvsAmdBallCoverBuild(res.get(), cp.p, d.get(), idx.get()), "cuvsAmdBallCoverBuild");
+  return idx;
+}
+// neighbors int64 [q, k] and distances fp32 [q, k], rows sorted by (distance, id); the defaults give brute force's answer
+inline void knn_query(const resources& res, const index& idx, device_matrix_view<const float> queries, device_matrix_view<int64_t> neighbors,
+                      device_matrix_view<float> distances, bool perform_post_filtering = true, float weight = 1.0f)
+{
+  detail::tensor<const float> q(queries);
+  detail::tensor<int64_t> n(neighbors);
+  detail::tensor<float> d(distances);
+  check(cuvsAmdBallCoverKnnQuery(res.get(), idx.get(), q.get(), n.get(), d.get(), perform_post_filtering, weight), "cuvsAmdBallCoverKnnQuery");
+}
+// build + the dataset queried against itself; returns the index
+inline index all_knn_query(const resources& res, const index_params& p, device_matrix_view<const float> dataset,
+                           device_matrix_view<int64_t> neighbors, device_matrix_view<float> distances, bool perform_post_filtering = true,
+                           float weight = 1.0f)
+{
+  c_index_params cp;
+  *cp.p = cuvsAmdBallCoverIndexParams{p.metric, p.n_landmarks, p.seed};
+  index idx;
+  detail::tensor<const float> x(dataset);
+  detail::tensor<int64_t> n(neighbors);
+  detail::tensor<float> d(distances);
+  check(cuvsAmdBallCoverAllKnnQuery(res.get(), cp.p, x.get(), n.get(), d.get(), perform_post_filtering, weight, idx.get()),
+        "cuvsAmdBallCoverAllKnnQuery");
+  return idx;
+}
+// eps_nn, dense: adj bool [q, m] and vd [q + 1] as epsilon_neighborhood::compute; eps is the radius
+template <typename IdxT>
+void eps_nn(const resources& res, const index& idx, device_matrix_view<const float> queries, device_matrix_view<bool> adj, IdxT* vd, float eps)
+{
+  detail::tensor<const float> q(queries);
+  detail::tensor<bool> ta(adj);
+  detail::vector_tensor<IdxT> tv(vd, queries.extent(0) + 1);
+  check(cuvsAmdBallCoverEpsNn(res.get(), idx.get(), q.get(), adj.ptr ? ta.get() : nullptr, tv.get(), eps), "cuvsAmdBallCoverEpsNn");
+}
+// eps_nn, CSR: the protocols of epsilon_neighborhood::csr
+inline void eps_nn(const resources& res, const index& idx, device_matrix_view<const float> queries, int64_t* indptr, int64_t* indices,
+                   float* distances, int64_t indices_len, int64_t* vd, float eps, int64_t* max_k = nullptr)
+{
+  detail::tensor<const float> q(queries);
+  detail::vector_tensor<int64_t> tp(indptr, queries.extent(0) + 1), ti(indices, indices_len), tv(vd, queries.extent(0) + 1);
+  detail::vector_tensor<float> td(distances, indices_len);
+  check(cuvsAmdBallCoverEpsNnCsr(res.get(), idx.get(), q.get(), tp.get(), ti.get(), td.get(), tv.get(), eps, max_k), "cuvsAmdBallCoverEpsNnCsr");
+}
+// the calling thread's last query: lists visited, rows scored, rows skipped by the window, queries
+inline std::array<uint64_t, 4> last_stats()
+{
+  std::array<uint64_t, 4> out{};
+  check(cuvsAmdBallCoverLastStats(out.data()), "cuvsAmdBallCoverLastStats");
+  return out;
+}
+}  // namespace ball_cover
+
 }  // namespace neighbors
 }  // namespace cuvs
 
-// the extensions (epsilon_neighborhood, ivf_rabitq entry points) are also reachable under the library's own name
+// the extensions (ball_cover, epsilon_neighborhood, ivf_rabitq entry points) are also reachable under the library's own name
 namespace cuvs_amd {
 namespace neighbors = ::cuvs::neighbors;
 }
