@@ -14,7 +14,8 @@
 //     and keeps the K best - no per-node locks: 288 GB of HBM pays for proposal buffers instead;
 //   * iterations stop after `n_iters` rounds or when fewer than 0.01 % of the list slots changed
 //     (nn_descent.cuh termination_threshold).
-// The result is approximate and depends on atomic ordering (as the reference's): tests check graph recall.
+// The result is approximate and depends on atomic ordering (as the reference's): tests check graph recall and the invariants of
+// every row; each kernel alone is compared with a CPU twin through cuvsAmdNnDescentStep (tests/test_nn_descent_steps_gpu.py).
 #include "ops.hpp"
 #include "device_utils.hpp"
 
@@ -92,7 +93,10 @@ __device__ inline uint32_t team_pair_key(const T* __restrict__ data, int64_t dim
   acc = acc + __shfl_xor(acc, 2, 64);
   acc = acc + __shfl_xor(acc, 4, 64);
   if (mode == 1) acc = -acc;                                   // inner product: larger is closer
-  if (mode == 2) acc = 1.0f - acc / (norms[a] * norms[b]);     // cosine
+  if (mode == 2) {  // cosine; a zero row is at distance 0 from every row (detail/nn_descent.cuh:534-537), never 0/0
+    const float np = norms[a] * norms[b];
+    acc            = np > 0.0f ? 1.0f - acc / np : 0.0f;
+  }
   return float_to_key(acc);
 }
 
@@ -340,6 +344,60 @@ __global__ void nnd_gather_bits_kernel(const uint8_t* __restrict__ data, int64_t
 }
 inline dim3 nnd_bits_grid(int64_t elems, int num_cus) { return dim3((unsigned)std::min<int64_t>((elems + 255) / 256, (int64_t)num_cus * 64)); }
 
+// ---------------------------------------------------------------- launches (nnd_run and the step hook share them)
+// a node's list and its proposals are merged in LDS, four nodes (waves) per workgroup
+struct nnd_merge_shape {
+  int np2;     // K + P rounded up to a power of two: the length of the bitonic sort
+  size_t lds;  // dynamic LDS of the workgroup: 4 waves x (keys + ids)
+};
+inline nnd_merge_shape nnd_merge_shape_of(const nnd_state& st)
+{
+  nnd_merge_shape m;
+  m.np2 = next_pow2((int)(st.K + st.P));
+  m.lds = (size_t)4 * 2 * m.np2 * sizeof(uint32_t);
+  return m;
+}
+
+template <typename T>
+void nnd_launch_init(resources& res, const nnd_state& st, const T* data, int64_t dim, int mode, const float* norms, uint64_t seed,
+                     const uint32_t* perm, const uint32_t* pos_of, const uint32_t* cl_off, const uint32_t* labels,
+                     const uint32_t* hubs, uint32_t n_hubs)
+{
+  hipLaunchKernelGGL((nnd_init_kernel<T>), dim3((unsigned)st.n), dim3(256), 0, res.stream, st, data, dim, mode, norms, seed, perm,
+                     pos_of, cl_off, labels, hubs, n_hubs);
+}
+
+inline void nnd_launch_merge(resources& res, const nnd_state& st)
+{
+  const nnd_merge_shape m = nnd_merge_shape_of(st);
+  CUVS_EXPECTS(m.lds <= 160 * 1024, "nn_descent: lists of %u entries + %u proposals do not fit the 4096 LDS entries of the merge step",
+               st.K, st.P);
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(nnd_merge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)m.lds));
+  hipLaunchKernelGGL(nnd_merge_kernel, dim3(grid_blocks(st.n, 4)), dim3(256), m.lds, res.stream, st, m.np2);
+}
+
+inline void nnd_launch_count_new(resources& res, const nnd_state& st)
+{
+  hipLaunchKernelGGL(nnd_count_new_kernel, dim3(grid_blocks(st.n * (int64_t)st.K, 256)), dim3(256), 0, res.stream, st);
+}
+
+inline void nnd_launch_sample(resources& res, const nnd_state& st)
+{
+  hipLaunchKernelGGL(nnd_sample_kernel, dim3(grid_blocks(st.n, 4)), dim3(256), 0, res.stream, st);
+}
+
+template <typename T>
+void nnd_launch_join(resources& res, const nnd_state& st, const T* data, int64_t dim, int mode, const float* norms)
+{
+  hipLaunchKernelGGL((nnd_join_kernel<T>), dim3((unsigned)st.n), dim3(kJoinThreads), 0, res.stream, st, data, dim, mode, norms);
+}
+
+inline int nnd_mode_of(int metric)
+{
+  return metric == M_BitwiseHamming ? kModeHamming : (metric == M_InnerProduct ? 1 : (metric == M_CosineExpanded ? 2 : 0));
+}
+
 template <typename T>
 void nnd_run(resources& res, const T* data, elem_t et, int64_t n, int64_t dim, uint32_t K_out, int mode, const float* norms,
              int n_iters, uint32_t* knn_out, uint32_t* keys_out, float termination_threshold)
@@ -363,16 +421,11 @@ void nnd_run(resources& res, const T* data, elem_t et, int64_t n, int64_t dim, u
   HIP_TRY(hipMemsetAsync(keys.data(), 0xff, keys.bytes(), res.stream));
   HIP_TRY(hipMemsetAsync(worst.data(), 0xff, worst.bytes(), res.stream));
   CUVS_EXPECTS(n < (int64_t(1) << 31), "nn_descent: at most 2^31 rows");
-  const int np2     = next_pow2((int)(K + P));
-  const size_t msm  = (size_t)4 * 2 * np2 * sizeof(uint32_t);
   // (a node's list and its proposals are merged in LDS: K + P = 3 x roundUp32(1.3 x degree) entries <= 4096, i.e. a graph degree up
   // to 1024 - the reference's own tables stop at 64; memory: n x (K + 2 P) x 8 bytes, ~30 GB at 10M rows and degree 128)
-  CUVS_EXPECTS(msm <= 160 * 1024,
+  CUVS_EXPECTS(nnd_merge_shape_of(st).lds <= 160 * 1024,
                "nn_descent: graph degree %u is too large for the merge step (internal lists of %u + %u proposals must fit 4096 LDS entries: "
                "at most degree 1024)", K_out, K, P);
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(nnd_merge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)msm));
-  const unsigned g4 = grid_blocks(n, 4);
   // ---- coarse clustering for the initial lists: clusters of ~4 K rows (balanced k-means on a strided sample)
   dev_buf<uint32_t> perm, pos_of, cl_off, labels;
   int64_t n_clusters = std::min<int64_t>(65536, n / (4 * (int64_t)K));
@@ -436,23 +489,22 @@ void nnd_run(resources& res, const T* data, elem_t et, int64_t n, int64_t dim, u
     row_norms<T>(res, data, n, dim, dim, sq.data(), false);
     select_k<uint32_t, uint32_t>(res, sq.data(), nullptr, 1, n, n, (int)n_hubs, hv.data(), hubs.data(), false);
   }
-  hipLaunchKernelGGL((nnd_init_kernel<T>), dim3((unsigned)n), dim3(256), 0, res.stream, st, data, dim, mode, norms,
-                     0x9E3779B97F4A7C15ull, perm.data(), pos_of.data(), cl_off.data(), labels.data(), hubs.data(), n_hubs);
-  hipLaunchKernelGGL(nnd_merge_kernel, dim3(g4), dim3(256), msm, res.stream, st, np2);
+  nnd_launch_init<T>(res, st, data, dim, mode, norms, 0x9E3779B97F4A7C15ull, perm.data(), pos_of.data(), cl_off.data(),
+                     labels.data(), hubs.data(), n_hubs);
+  nnd_launch_merge(res, st);
   for (int it = 0; it < n_iters; ++it) {
     HIP_TRY(hipMemsetAsync(rev_new_cnt.data(), 0, rev_new_cnt.bytes(), res.stream));
     HIP_TRY(hipMemsetAsync(rev_old_cnt.data(), 0, rev_old_cnt.bytes(), res.stream));
     HIP_TRY(hipMemsetAsync(n_updates.data(), 0, sizeof(unsigned long long), res.stream));
-    hipLaunchKernelGGL(nnd_count_new_kernel, dim3(grid_blocks(n * K, 256)), dim3(256), 0, res.stream, st);
+    nnd_launch_count_new(res, st);
     unsigned long long upd = 0;
     copy_async(res, &upd, n_updates.data(), sizeof(upd));
     sync(res);
     // nn_descent.cuh: stop when fewer than termination_threshold (1e-4) of the n*K slots changed
     if (it > 0 && (double)upd < (double)termination_threshold * (double)n * (double)K) break;
-    hipLaunchKernelGGL(nnd_sample_kernel, dim3(g4), dim3(256), 0, res.stream, st);
-    hipLaunchKernelGGL((nnd_join_kernel<T>), dim3((unsigned)n), dim3(kJoinThreads), 0, res.stream, st, data, dim, mode,
-                       norms);
-    hipLaunchKernelGGL(nnd_merge_kernel, dim3(g4), dim3(256), msm, res.stream, st, np2);
+    nnd_launch_sample(res, st);
+    nnd_launch_join<T>(res, st, data, dim, mode, norms);
+    nnd_launch_merge(res, st);
     HIP_TRY(hipGetLastError());
   }
   // ids without flags -> output (invalid entries stay 0xffffffff)
@@ -487,8 +539,7 @@ void knn_graph_nn_descent(resources& res, const void* data, elem_t et, int64_t n
   // detail/nn_descent.cuh:1495-1498
   CUVS_EXPECTS(metric != M_BitwiseHamming || et == elem_t::u8 || et == elem_t::i8,
                "Data type needs to be int8 or uint8 for NN Descent to run with BitwiseHamming distance.");
-  const int mode = metric == M_BitwiseHamming ? kModeHamming
-                                              : (metric == M_InnerProduct ? 1 : (metric == M_CosineExpanded ? 2 : 0));
+  const int mode = nnd_mode_of(metric);
   CUVS_EXPECTS(mode != 2 || norms != nullptr, "nn_descent: cosine needs row norms");
   if (n_iters <= 0) n_iters = 20;
   switch (et) {
@@ -504,6 +555,90 @@ void knn_graph_nn_descent(resources& res, const void* data, elem_t et, int64_t n
 }
 
 }  // namespace cuvs_amd
+
+// test hook (not part of the reference ABI): ONE step of the descent on caller-owned device buffers, launched exactly as
+// nnd_run launches it (grid, block, dynamic LDS). The caller owns every array of the state and keeps its invariants: list and
+// sample ids below n (or 0xffffffff), lists sorted, rev_*_cnt zeroed before `sample`, prop_cnt zeroed before `join`.
+// step: 0 init, 1 merge, 2 sample, 3 join, 4 count_new. elem: 0 f32, 1 f16, 2 i8, 3 u8. metric: a cuvsDistanceType.
+struct cuvsAmdNnDescentStepArgs {
+  uint32_t *ids, *keys, *worst, *prop_ids, *prop_keys, *prop_cnt;              // [n, K] [n, K] [n] [n, P] [n, P] [n]
+  uint32_t *fwd_new, *fwd_old, *rev_new, *rev_old, *rev_new_cnt, *rev_old_cnt; // [n, 32] x 4, [n] x 2
+  unsigned long long* n_updates;                                              // count_new adds to it
+  int64_t n;
+  uint32_t K, P;
+  const void* data;    // init, join: [n, dim] rows of type elem
+  int64_t dim;
+  int32_t elem, metric;
+  const float* norms;  // cosine: |row|
+  uint64_t seed;       // init
+  const uint32_t *perm, *pos_of, *cl_off, *labels;  // init: the clustering (all four, or all null)
+  const uint32_t* hubs;                             // init: optional
+  uint32_t n_hubs;
+};
+
+extern "C" __attribute__((visibility("default"))) int cuvsAmdNnDescentStep(uintptr_t res_h, int step,
+                                                                            const cuvsAmdNnDescentStepArgs* args)
+{
+  using namespace cuvs_amd;
+  return translate_exceptions([=] {
+    auto& res = *reinterpret_cast<resources*>(res_h);
+    CUVS_EXPECTS(args != nullptr, "args is null");
+    const cuvsAmdNnDescentStepArgs& a = *args;
+    CUVS_EXPECTS(a.n >= 1 && a.n < (int64_t(1) << 31) && a.K >= 1 && a.P >= 1, "nn_descent step: bad n, K or P");
+    nnd_state st;
+    st.ids = a.ids; st.keys = a.keys; st.worst = a.worst; st.prop_ids = a.prop_ids; st.prop_keys = a.prop_keys;
+    st.prop_cnt = a.prop_cnt; st.fwd_new = a.fwd_new; st.fwd_old = a.fwd_old; st.rev_new = a.rev_new; st.rev_old = a.rev_old;
+    st.rev_new_cnt = a.rev_new_cnt; st.rev_old_cnt = a.rev_old_cnt; st.n_updates = a.n_updates; st.n = a.n; st.K = a.K; st.P = a.P;
+    const bool lists = a.ids && a.keys, props = a.prop_ids && a.prop_keys && a.prop_cnt;
+    const bool samples = a.fwd_new && a.fwd_old && a.rev_new && a.rev_old && a.rev_new_cnt && a.rev_old_cnt;
+    const int mode = nnd_mode_of(a.metric);
+    if (step == 0 || step == 3) {
+      CUVS_EXPECTS(a.data != nullptr && a.dim >= 1 && a.elem >= 0 && a.elem <= 3, "nn_descent step: rows are missing");
+      CUVS_EXPECTS(mode != kModeHamming || a.elem >= 2, "nn_descent step: BitwiseHamming needs int8 or uint8 rows");
+      CUVS_EXPECTS(mode != 2 || a.norms != nullptr, "nn_descent step: cosine needs row norms");
+    }
+    auto typed = [&](auto fn) {
+      switch ((elem_t)a.elem) {
+        case elem_t::f32: fn(static_cast<const float*>(a.data)); break;
+        case elem_t::f16: fn(static_cast<const __half*>(a.data)); break;
+        case elem_t::i8: fn(static_cast<const int8_t*>(a.data)); break;
+        case elem_t::u8: fn(static_cast<const uint8_t*>(a.data)); break;
+      }
+    };
+    switch (step) {
+      case 0: {
+        CUVS_EXPECTS(props, "nn_descent step: init writes the proposal buffers");
+        const bool clustered = a.perm != nullptr;
+        CUVS_EXPECTS(clustered == (a.pos_of != nullptr) && clustered == (a.cl_off != nullptr) && clustered == (a.labels != nullptr),
+                     "nn_descent step: perm, pos_of, cl_off and labels come together");
+        CUVS_EXPECTS(a.n_hubs == 0 || a.hubs != nullptr, "nn_descent step: n_hubs without hubs");
+        typed([&](auto* rows) {
+          nnd_launch_init(res, st, rows, a.dim, mode, a.norms, a.seed, a.perm, a.pos_of, a.cl_off, a.labels, a.hubs, a.n_hubs);
+        });
+        break;
+      }
+      case 1:
+        CUVS_EXPECTS(lists && props && a.worst, "nn_descent step: merge needs the lists, worst and the proposal buffers");
+        nnd_launch_merge(res, st);
+        break;
+      case 2:
+        CUVS_EXPECTS(lists && samples, "nn_descent step: sample needs the lists and the sample buffers");
+        nnd_launch_sample(res, st);
+        break;
+      case 3:
+        CUVS_EXPECTS(props && samples && a.worst, "nn_descent step: join needs the samples, worst and the proposal buffers");
+        typed([&](auto* rows) { nnd_launch_join(res, st, rows, a.dim, mode, a.norms); });
+        break;
+      case 4:
+        CUVS_EXPECTS(a.ids && a.n_updates, "nn_descent step: count_new needs the ids and the counter");
+        nnd_launch_count_new(res, st);
+        break;
+      default: CUVS_EXPECTS(false, "nn_descent step: unknown step %d", step);
+    }
+    HIP_TRY(hipGetLastError());
+    sync(res);
+  });
+}
 
 // test / bench hook (not part of the reference ABI): NN-descent kNN graph of device fp32 rows
 extern "C" __attribute__((visibility("default"))) int cuvsAmdNnDescent(uintptr_t res_h, const float* data, int64_t n,

@@ -277,3 +277,9 @@ REFINE_CASES = [(137, 1000, 16, k, 33, metric, host) for k in (1, 10, 33) for me
 # (self included), eps 0.001 (:150-158). BitwiseHamming / L1 rows are listed and skipped (outside this repo's scope).
 NN_DESCENT_CASES = [(n, d, deg, metric, host, 0.90) for n in (2000, 4000) for d in (4, 16, 31, 64, 256, 1024) for deg in (32, 64)
                     for metric in ("bitwise_hamming", L2, L2S, IP, COS, "l1") for host in (False, True)]
+# The same table is instantiated for int8 and uint8 rows (ann_nn_descent/test_int8_t_uint32_t.cu, test_uint8_t_uint32_t.cu): int8
+# rows uniform integers [-5, 5), uint8 [0, 5) (ann_nn_descent.cuh:164-173). Rows of the table with the element type in front, over
+# dim {4, 31, 256} and the metrics other than BitwiseHamming (its rows are NN_DESCENT_CASES', run by test_hamming_gpu.py); L1 is
+# listed and skipped. f16 has no instantiation in the reference: the same rows, over the float inputs rounded to half.
+NN_DESCENT_TYPED_CASES = [(dt, n, d, deg, metric, host, 0.90) for dt in ("i8", "u8", "f16") for n in (2000, 4000) for d in (4, 31, 256)
+                          for deg in (32, 64) for metric in (L2, L2S, IP, COS, "l1") for host in (False, True)]

@@ -368,3 +368,34 @@ def test_nn_descent_reference_table(case, res):
     dist = index.distances
     td, ti = _naive_knn(x, x, degree, metric)     # the exact kNN graph (a row is its own nearest neighbour, as in the reference)
     _eval_neighbours(ti, graph, td, dist, 0.001, min_recall, test_unique=False)
+
+
+def _nn_descent_typed_params():
+    out = []
+    for n, c in enumerate(T.NN_DESCENT_TYPED_CASES):
+        marks = [pytest.mark.skip(reason="metric outside this repo's scope (DESIGN 7)")] if c[4] == "l1" else []
+        out.append(pytest.param(c, id=f"{c[0]}-inputs-{n:03d}-{c[4]}-n{c[1]}-d{c[2]}-deg{c[3]}-{'host' if c[5] else 'device'}", marks=marks))
+    return out
+
+
+@pytest.mark.parametrize("case", _nn_descent_typed_params())
+def test_nn_descent_reference_table_typed_rows(case, res):
+    """The table above for int8 / uint8 rows (the reference's generators: uniform integers [-5, 5) / [0, 5), seed 1234) and for
+    f16 rows (the float inputs rounded to half - exact in fp32, so the exact graph is that of the rounded values)."""
+    import torch
+    from cuvs_amd.neighbors import nn_descent
+
+    dt, n, dim, degree, metric, host, min_recall = case
+    g = torch.Generator(device="cuda")
+    g.manual_seed(1234)
+    if dt == "f16":
+        x = (torch.randn((n, dim), generator=g, device="cuda") * 2.0 + 0.1).half()
+    else:
+        lo, hi, tdt = (-5, 5, torch.int8) if dt == "i8" else (0, 5, torch.uint8)
+        x = torch.randint(lo, hi, (n, dim), generator=g, device="cuda", dtype=torch.int32).to(tdt)
+    index = nn_descent.build(nn_descent.IndexParams(metric=metric, graph_degree=degree, intermediate_graph_degree=2 * degree, max_iterations=100),
+                             x.cpu().numpy() if host else x, resources=res)
+    graph = index.graph.to(torch.int64) & 0xFFFFFFFF
+    dist = index.distances
+    td, ti = _naive_knn(x, x, degree, metric)
+    _eval_neighbours(ti, graph, td, dist, 0.001, min_recall)   # with the uniqueness of a row's ids: n > degree, every slot is valid
