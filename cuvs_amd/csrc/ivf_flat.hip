@@ -13,7 +13,7 @@
 // the scalar cache, so the 8 fma chains per loaded element (4 packed fp32 add + 4 packed fp32 fma) cost no LDS
 // cycles. Per-wave register top lists + shared k-th bounds, two-phase schedule and a per-tile early stop as in
 // the PQ scan. Cosine = dot products + in-kernel row norms. In-list order is ascending source id.
-#include "ivf_common.hpp"
+#include "ivf_list_scan.hpp"
 #include "ivf_lists.hpp"
 #include "ivf_pq_scan3.hpp"
 
@@ -103,28 +103,10 @@ __global__ void pack_rows_kernel(pack_args a)
   if (ch == 0) a.indices[fr] = a.new_ids ? a.new_ids[row] : a.id_base + (int64_t)row;
 }
 
-struct flat_scan_args {
-  const work_item* items;
-  const uint32_t* item_begin;  // device scalars: this launch covers items [*item_begin, *item_end); nullptr: from 0
-  const uint32_t* item_end;
-  uint32_t n_lists;            // item.list >= n_lists: tail-phase label of list item.list - n_lists
-  const uint32_t* sorted_pairs;
+struct flat_scan_args : list_scan_args {
   const void* queries;  // [n_queries, dim] of T (raw values)
-  const float* qtiles;  // [n_items, dim_pad, QPB] fp32 query tile of every work item (flat_query_tiles_kernel)
-  const uint8_t* data;
-  const uint32_t* list_offsets;
-  const uint32_t* list_sizes;
-  float* out_d;
-  uint32_t* out_i;
-  uint32_t* query_kth;
-  const uint32_t* filter_bits;  // optional bitset over source ids (1 keeps), sample_filter.cuh semantics
-  const int64_t* indices;       // flat row -> source id (only read when filtering)
-  uint32_t n_probes, dim, veclen, n_chunks, k;
+  uint32_t dim, veclen;
   int is_ip;  // 0: L2, 1: inner product, 2: cosine
-  float* all_scores;         // non-fused path (large k, ivf_common.hpp): [n_queries, scores_ld] score of every probed row
-  uint32_t* all_rows;        //   flat row of every column (0xffffffff: nothing there)
-  const uint32_t* pair_seg;  //   first column of each pair in its query's row
-  size_t scores_ld;
   const uint32_t* run_if = nullptr;  // optional device word: the launch does nothing when it is zero (fallback pass decided on the device)
 };
 
@@ -211,18 +193,6 @@ __global__ void flat_query_tiles_int_kernel(const work_item* __restrict__ items,
   }
 }
 
-// the compiler sinks every load of a group to its first use (one load, one wait, sixteen fmas, next load ...); an empty asm that
-// takes all four as operands keeps them issued back to back
-__device__ inline void keep_loads_together(uint4 (&w)[kStopEvery])
-{
-  static_assert(kStopEvery == 4, "four chunks per group");
-  // (not volatile: an asm with unmodelled side effects counts as a memory clobber, and the wave-uniform loads of the query tile
-  // stop being scalar loads)
-  asm(""
-      : "+v"(w[0].x), "+v"(w[0].y), "+v"(w[0].z), "+v"(w[0].w), "+v"(w[1].x), "+v"(w[1].y), "+v"(w[1].z), "+v"(w[1].w),
-                 "+v"(w[2].x), "+v"(w[2].y), "+v"(w[2].z), "+v"(w[2].w), "+v"(w[3].x), "+v"(w[3].y), "+v"(w[3].z), "+v"(w[3].w));
-}
-
 // IP (inner product) is a template argument: tested at run time inside the unrolled element loop it became a
 // scalar branch per element
 // ALL: the non-fused path (every score written out, no top lists) - a template argument so that the fused kernels
@@ -236,45 +206,23 @@ __global__ __launch_bounds__(kFlatThreads) void ivf_flat_scan_kernel(flat_scan_a
   constexpr bool INT = (std::is_same_v<T, int8_t> || std::is_same_v<T, uint8_t>) && METRIC != 2;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   if (a.run_if != nullptr && *a.run_if == 0u) return;
-  const uint32_t item0 = a.item_begin ? *a.item_begin : 0u;
-  const uint32_t w     = item0 + blockIdx.x;
-  if (w >= *a.item_end) return;
-  const work_item item = a.items[w];
-
+  list_scan_item s;
+  if (!list_scan_begin<QPB, kFlatWaves>(a, smem, s)) return;
   const uint32_t dim_pad = a.n_chunks * VL;
-  const size_t off = (((size_t)QPB * kFlatWaves * a.k * 8) + 15) & ~size_t(15);  // merge area
-  uint32_t* kthb = reinterpret_cast<uint32_t*>(smem + off);
-  uint32_t* pid  = kthb + 16;
-
-  const int tid  = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const uint32_t L        = item.list >= a.n_lists ? item.list - a.n_lists : item.list;
-  const uint32_t base_row = a.list_offsets[L];
-  const uint32_t len      = a.list_sizes[L];
-
-  if (tid < QPB) {
-    const uint32_t p = tid < (int)item.count ? a.sorted_pairs[item.first + tid] : 0xffffffffu;
-    pid[tid]         = p;
-    kthb[tid]        = p != 0xffffffffu ? a.query_kth[p / a.n_probes] : 0u;
-  }
-  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
   // wave-uniform pointer: the loads below become s_load_dwordx8 (scalar cache -> SGPRs)
-  const float* __restrict__ qt = a.qtiles + (size_t)w * (dim_pad + 1) * QPB;
+  const float* __restrict__ qt = a.qtiles + (size_t)s.w * (dim_pad + 1) * QPB;
 
-  wave_top<E> top[QPB];
-#pragma unroll
-  for (int j = 0; j < QPB; ++j) top[j].init();
-  const int kr          = (int)a.k - 1;
-  uint32_t fresh        = 0xffu;  // bit j: this wave's list of query j is still empty (wave-uniform)
-  const size_t g0       = (size_t)(base_row >> 6);
+  list_scan_tops<QPB, E> tops;
+  tops.init();
+  const size_t g0       = (size_t)(s.base_row >> 6);
   const uint4* data16   = reinterpret_cast<const uint4*>(a.data);
-  const uint32_t n_tile = (len + 63) / 64;
+  const uint32_t n_tile = (s.len + 63) / 64;
 
   for (uint32_t tile = wave; tile < n_tile; tile += kFlatWaves) {
     const uint32_t tile0 = tile * 64;
-    const uint32_t v     = tile0 + lane;
-    const bool valid     = v < len;
+    const bool valid     = tile0 + lane < s.len;
     // two queries per packed fp32 instruction (v_pk_add_f32 / v_pk_fma_f32): lane by lane the IEEE operations of
     // the scalar form; (q - x)^2 == (x - q)^2 exactly
     f32x2_t accv[QPB / 2];
@@ -284,12 +232,13 @@ __global__ __launch_bounds__(kFlatThreads) void ivf_flat_scan_kernel(flat_scan_a
     const uint4* cp = data16 + ((g0 + tile) * a.n_chunks) * 64 + lane;
     // early stop (L2): partial sums of squares only grow, so once every row of the tile is above the k-th bound of
     // every query of the item the rest of the row data is neither loaded nor accumulated. Bounds are read once
-    // per tile and only decrease: rows dropped here are also rejected by the filter below.
+    // per tile and only decrease: rows dropped here are also rejected by the admission below.
+    // (this loop stands in both scan kernels: as a function of ivf_list_scan.hpp it cost <__half, 4, 0, false> an occupancy step)
     float bf[QPB];
 #pragma unroll
     for (int j = 0; j < QPB; ++j) {
-      const uint32_t kk = __builtin_amdgcn_readfirstlane(kthb[j]);
-      bf[j] = (IP || j >= (int)item.count) ? -INFINITY : (kk >= 0xff800000u ? INFINITY : key_to_float(kk));
+      const uint32_t kk = __builtin_amdgcn_readfirstlane(s.kthb[j]);
+      bf[j] = (IP || j >= (int)s.item.count) ? -INFINITY : (kk >= 0xff800000u ? INFINITY : key_to_float(kk));
     }
     float acc[QPB];
     if constexpr (INT) {
@@ -400,144 +349,13 @@ __global__ __launch_bounds__(kFlatThreads) void ivf_flat_scan_kernel(flat_scan_a
     }
 #pragma unroll
     for (int j = 0; j < QPB; ++j) {
-      if (j >= (int)item.count) break;
-      const float dj       = IP ? -acc[j] : acc[j];  // smaller is better
-      if constexpr (ALL) {  // non-fused path: every score goes to the query's row (filtered rows keep the fill)
-        bool keep = valid;
-        if (keep && a.filter_bits != nullptr) {
-          const int64_t sid = a.indices[(size_t)base_row + v];
-          keep              = (a.filter_bits[sid >> 5] >> (sid & 31)) & 1u;
-        }
-        const uint32_t p = pid[j];
-        if (keep) {
-          const size_t o  = (size_t)(p / a.n_probes) * a.scores_ld + a.pair_seg[p] + v;
-          a.all_scores[o] = dj;
-          a.all_rows[o]   = base_row + v;
-        }
-        continue;
-      }
-      const uint32_t bound = kthb[j];
-      unsigned long long m = __ballot(valid && float_to_key(dj) <= bound);
-      if (m == 0ull) continue;
-      // the wave's first candidates of query j (its list is empty: cold bounds let nearly every row of the first tile through):
-      // one sorting network instead of up to 64 serial insertions - the list that results is the same, entry for entry
-      const bool first = ((fresh >> j) & 1u) != 0u;
-      fresh &= ~(1u << j);
-      if (first && a.filter_bits == nullptr && __popcll(m) >= 12 && __ballot(dj != dj) == 0ull) {
-        const bool c = ((m >> lane) & 1ull) != 0ull;
-        float sd     = c ? dj : INFINITY;
-        uint32_t si  = c ? tile0 + (uint32_t)lane : 0xffffffffu;
-        wave_sort64(sd, si, lane);
-        top[j].d[0] = sd;
-        top[j].i[0] = si;
-        const float kd0 = top[j].rank_d(kr);
-        if (lane == 0 && kd0 < INFINITY) atomicMin(&kthb[j], float_to_key(kd0));
-        continue;
-      }
-      float kd      = top[j].rank_d(kr);
-      uint32_t ki   = top[j].rank_i(kr);
-      bool improved = false;
-      while (m != 0ull) {
-        const int src = (int)__ffsll((long long)m) - 1;
-        m &= m - 1ull;
-        const float cd    = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(dj), src));
-        const uint32_t ci = tile0 + (uint32_t)src;
-        if (a.filter_bits != nullptr) {  // pre-filter: rows whose source id is masked out never enter the top list
-          const int64_t sid = a.indices[(size_t)base_row + ci];
-          if (!((a.filter_bits[sid >> 5] >> (sid & 31)) & 1u)) continue;
-        }
-        if ((cd < kd) || (cd == kd && ci < ki)) {
-          top[j].insert(cd, ci, lane);
-          kd       = top[j].rank_d(kr);
-          ki       = top[j].rank_i(kr);
-          improved = true;
-        }
-      }
-      if (improved && lane == 0 && kd < INFINITY) atomicMin(&kthb[j], float_to_key(kd));
+      if (j >= (int)s.item.count) break;
+      list_scan_offer<QPB, E, ALL>(a, s, j, IP ? -acc[j] : acc[j], tile0, lane, tops);  // smaller is better
     }
   }
 
-  if constexpr (ALL) return;
-  // ---- merge the wave lists (the query tile is no longer needed)
-  __syncthreads();
-  if constexpr (E > 1) {
-    // k > 64: the sorted wave lists are merged by the whole workgroup, one query after the other (ivf_common.hpp)
-    constexpr int KP2 = E == 2 ? 128 : 256;
-    float* sd    = reinterpret_cast<float*>(smem);
-    uint32_t* si = reinterpret_cast<uint32_t*>(smem + (size_t)kFlatWaves * KP2 * 4);
-    for (int j = 0; j < QPB; ++j) {
-      if (j >= (int)item.count) break;  // workgroup-uniform
-#pragma unroll
-      for (int e = 0; e < E; ++e) {
-        const int r = e * 64 + lane;
-        const bool in = r < (int)a.k;
-        sd[wave * KP2 + r] = in ? top[j].d[e] : INFINITY;
-        si[wave * KP2 + r] = in ? top[j].i[e] : 0xffffffffu;
-      }
-      __syncthreads();
-      merge_sorted_lists<kFlatThreads>(sd, si, kFlatWaves, KP2, tid);
-      const size_t o = (size_t)pid[j] * a.k;
-      for (int r = tid; r < (int)a.k; r += kFlatThreads) {
-        const bool ok  = si[r] != 0xffffffffu;
-        a.out_d[o + r] = ok ? sd[r] : FLT_MAX;
-        a.out_i[o + r] = ok ? base_row + si[r] : 0xffffffffu;
-      }
-      if (tid == 0 && si[a.k - 1] != 0xffffffffu && sd[a.k - 1] < INFINITY)
-        atomicMin(&a.query_kth[pid[j] / a.n_probes], float_to_key(sd[a.k - 1]));
-      __syncthreads();  // the next query reuses the area
-    }
-    return;
-  }
-  float* mg_d    = reinterpret_cast<float*>(smem);
-  uint32_t* mg_i = reinterpret_cast<uint32_t*>(smem + (size_t)QPB * kFlatWaves * a.k * 4);
-#pragma unroll
-  for (int j = 0; j < QPB; ++j) {
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      const int r = e * 64 + lane;
-      if (r < (int)a.k) {
-        mg_d[((size_t)j * kFlatWaves + wave) * a.k + r] = top[j].d[e];
-        mg_i[((size_t)j * kFlatWaves + wave) * a.k + r] = top[j].i[e];
-      }
-    }
-  }
-  __syncthreads();
-  if (wave < QPB && wave < (int)item.count) {
-    const int j = wave;
-    wave_top<E> fin;
-    fin.init();
-    float kd    = INFINITY;
-    uint32_t ki = 0xffffffffu;
-    const int n = kFlatWaves * (int)a.k;
-    for (int b0 = 0; b0 < n; b0 += 64) {
-      float md    = INFINITY;
-      uint32_t mi = 0xffffffffu;
-      if (b0 + lane < n) { md = mg_d[(size_t)j * n + b0 + lane]; mi = mg_i[(size_t)j * n + b0 + lane]; }
-      unsigned long long m = __ballot(mi != 0xffffffffu && ((md < kd) || (md == kd && mi < ki)));
-      while (m != 0ull) {
-        const int src = (int)__ffsll((long long)m) - 1;
-        m &= m - 1ull;
-        const float cd    = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(md), src));
-        const uint32_t ci = __builtin_amdgcn_readlane(mi, src);
-        if ((cd < kd) || (cd == kd && ci < ki)) {
-          fin.insert(cd, ci, lane);
-          kd = fin.rank_d(kr);
-          ki = fin.rank_i(kr);
-        }
-      }
-    }
-    const size_t o = (size_t)pid[j] * a.k;
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      int r = e * 64 + lane;
-      if (r < (int)a.k) {
-        bool ok        = fin.i[e] != 0xffffffffu;
-        a.out_d[o + r] = ok ? fin.d[e] : FLT_MAX;
-        a.out_i[o + r] = ok ? base_row + fin.i[e] : 0xffffffffu;
-      }
-    }
-    if (lane == 0 && kd < INFINITY) atomicMin(&a.query_kth[pid[j] / a.n_probes], float_to_key(kd));
-  }
+  // (the query tile is no longer needed)
+  if constexpr (!ALL) list_scan_merge<QPB, kFlatWaves, E>(a, s, smem, tops);
 }
 
 // the first `seg` slots of every query's candidate row (the head pairs' segments) start out "nothing found"
@@ -593,30 +411,13 @@ __global__ void unpack_flat_list_kernel(const uint8_t* __restrict__ data, uint32
   for (uint32_t b = 0; b < esz; ++b) out[i * esz + b] = data[addr + b];
 }
 
-template <typename T, int E, int METRIC, bool ALL = false>
-void launch_flat_scan_kern(resources& res, const flat_scan_args& a, size_t smem, unsigned grid)
-{
-  auto kern = ivf_flat_scan_kernel<T, E, METRIC, ALL>;
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kFlatThreads), smem, res.stream, a);
-}
-
 template <typename T>
 void launch_flat_scan(resources& res, const flat_scan_args& a, size_t smem, unsigned grid, bool big_k)
 {
-  if (a.all_scores != nullptr) {
-    if (a.is_ip == 2)      launch_flat_scan_kern<T, 1, 2, true>(res, a, smem, grid);
-    else if (a.is_ip == 1) launch_flat_scan_kern<T, 1, 1, true>(res, a, smem, grid);
-    else                   launch_flat_scan_kern<T, 1, 0, true>(res, a, smem, grid);
-  } else if (big_k) {
-    if (a.is_ip == 2)      launch_flat_scan_kern<T, 4, 2>(res, a, smem, grid);
-    else if (a.is_ip == 1) launch_flat_scan_kern<T, 4, 1>(res, a, smem, grid);
-    else                   launch_flat_scan_kern<T, 4, 0>(res, a, smem, grid);
-  } else {
-    if (a.is_ip == 2)      launch_flat_scan_kern<T, 1, 2>(res, a, smem, grid);
-    else if (a.is_ip == 1) launch_flat_scan_kern<T, 1, 1>(res, a, smem, grid);
-    else                   launch_flat_scan_kern<T, 1, 0>(res, a, smem, grid);
-  }
+  list_scan_dispatch(a.all_scores != nullptr, big_k, a.is_ip, [&](auto e, auto metric, auto all) {
+    list_scan_launch(res, ivf_flat_scan_kernel<T, decltype(e)::value, decltype(metric)::value, decltype(all)::value>, kFlatThreads, a,
+                     smem, grid);
+  });
   HIP_TRY(hipGetLastError());
 }
 
@@ -715,7 +516,7 @@ void ivf_flat_search(resources& res, const ivf_flat_index& idx, uint32_t n_probe
   const bool big_k        = k > 64 && !large_k;
   const int k_scan        = large_k ? 1 : k;
   const uint32_t dim_pad  = idx.n_chunks * idx.veclen;
-  size_t smem = ((((size_t)qpb * kFlatWaves * k_scan * 8) + 15) & ~size_t(15)) + 2 * 16 * 4;  // (>= 16 KiB at k > 64: the workgroup merge's 8 x 256 entries)
+  size_t smem = list_scan_smem_bytes(qpb, kFlatWaves, (uint32_t)k_scan);  // (>= 16 KiB at k > 64: the workgroup merge's 8 x 256 entries)
   const size_t scores_ld  = large_k ? largest_lists_total(idx.h_list_sizes, n_probes) : 0;
 
   // the matrix-core tail phase serves this index: beyond 256 dimensions fp32 / fp16 rows only (the re-score's fp32 chain over int8 /

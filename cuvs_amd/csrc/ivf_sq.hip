@@ -12,7 +12,7 @@
 // terms ([dim_pad][8] fp32 per item) and the per-dimension quantizer values are read with wave-uniform addresses
 // (scalar cache -> SGPRs). Per-wave register top lists with shared k-th bounds (k <= 256), or every score written out
 // and selected (k > 256). DESIGN 3.2 has the arithmetic contract.
-#include "ivf_common.hpp"
+#include "ivf_list_scan.hpp"
 #include "ivf_lists.hpp"
 #include "npy_io.hpp"
 
@@ -198,37 +198,10 @@ __global__ void sq_query_tiles_kernel(const work_item* __restrict__ items, const
     out[(size_t)dim_pad * QPB + threadIdx.x] = (qnorm != nullptr && qid[threadIdx.x] != 0xffffffffu) ? qnorm[qid[threadIdx.x]] : 0.f;
 }
 
-struct sq_scan_args {
-  const work_item* items;
-  const uint32_t* item_begin;  // device scalars: this launch covers items [*item_begin, *item_end); nullptr: from 0
-  const uint32_t* item_end;
-  uint32_t n_lists;            // item.list >= n_lists: tail-phase label of list item.list - n_lists
-  const uint32_t* sorted_pairs;
-  const float* qtiles;         // [n_items, dim_pad + 1, QPB]
-  const float* delta_pad;      // [dim_pad]
-  const float* aux;            // [n_lists, dim_pad] (dot products)
-  const uint8_t* data;
-  const uint32_t* list_offsets;
-  const uint32_t* list_sizes;
-  float* out_d;
-  uint32_t* out_i;
-  uint32_t* query_kth;
-  const uint32_t* filter_bits;  // optional bitset over source ids (1 keeps)
-  const int64_t* indices;
-  uint32_t n_probes, n_chunks, k;
-  float* all_scores;            // non-fused path (k > 256): [n_queries, scores_ld] score of every probed row
-  uint32_t* all_rows;           //   flat row of every column
-  const uint32_t* pair_seg;     //   first column of each pair in its query's row
-  size_t scores_ld;
+struct sq_scan_args : list_scan_args {
+  const float* delta_pad;  // [dim_pad]
+  const float* aux;        // [n_lists, dim_pad] (dot products)
 };
-
-// keeps the four chunk loads of a group issued back to back (see ivf_flat.hip keep_loads_together)
-__device__ inline void sq_keep_loads_together(uint4 (&w)[kSqStop])
-{
-  asm(""
-      : "+v"(w[0].x), "+v"(w[0].y), "+v"(w[0].z), "+v"(w[0].w), "+v"(w[1].x), "+v"(w[1].y), "+v"(w[1].z), "+v"(w[1].w),
-        "+v"(w[2].x), "+v"(w[2].y), "+v"(w[2].z), "+v"(w[2].w), "+v"(w[3].x), "+v"(w[3].y), "+v"(w[3].z), "+v"(w[3].w));
-}
 
 // METRIC 0: L2 (both variants), 1: inner product, 2: cosine. ALL: the non-fused path (every score written out).
 // Per (pair, dim): L2 diff = fma(-code, delta_d, qt_d), acc = fma(diff, diff, acc); dot products v = fma(code, delta_d, aux_d)
@@ -240,57 +213,35 @@ __global__ __launch_bounds__(kSqThreads) void ivf_sq_scan_kernel(sq_scan_args a)
   constexpr int QPB = kSqQPB;
   constexpr bool IP = METRIC != 0;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const uint32_t item0 = a.item_begin ? *a.item_begin : 0u;
-  const uint32_t w     = item0 + blockIdx.x;
-  if (w >= *a.item_end) return;
-  const work_item item = a.items[w];
-
+  list_scan_item s;
+  if (!list_scan_begin<QPB, kSqWaves>(a, smem, s)) return;
   const uint32_t dim_pad = a.n_chunks * 16;
-  const size_t off = (((size_t)QPB * kSqWaves * a.k * 8) + 15) & ~size_t(15);  // merge area
-  uint32_t* kthb = reinterpret_cast<uint32_t*>(smem + off);
-  uint32_t* pid  = kthb + 16;
-
-  const int tid  = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const uint32_t L        = item.list >= a.n_lists ? item.list - a.n_lists : item.list;
-  const uint32_t base_row = a.list_offsets[L];
-  const uint32_t len      = a.list_sizes[L];
-
-  if (tid < QPB) {
-    const uint32_t p = tid < (int)item.count ? a.sorted_pairs[item.first + tid] : 0xffffffffu;
-    pid[tid]         = p;
-    kthb[tid]        = p != 0xffffffffu ? a.query_kth[p / a.n_probes] : 0u;
-  }
-  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
   // wave-uniform pointers: scalar loads
-  const float* __restrict__ qt  = a.qtiles + (size_t)w * (dim_pad + 1) * QPB;
+  const float* __restrict__ qt  = a.qtiles + (size_t)s.w * (dim_pad + 1) * QPB;
   const float* __restrict__ dl  = a.delta_pad;
-  const float* __restrict__ aux = IP ? a.aux + (size_t)L * dim_pad : nullptr;
+  const float* __restrict__ aux = IP ? a.aux + (size_t)s.L * dim_pad : nullptr;
 
-  wave_top<E> top[QPB];
-#pragma unroll
-  for (int j = 0; j < QPB; ++j) top[j].init();
-  const int kr          = (int)a.k - 1;
-  uint32_t fresh        = 0xffu;  // bit j: this wave's list of query j is still empty (wave-uniform)
-  const size_t g0       = (size_t)(base_row >> 6);
+  list_scan_tops<QPB, E> tops;
+  tops.init();
+  const size_t g0       = (size_t)(s.base_row >> 6);
   const uint4* data16   = reinterpret_cast<const uint4*>(a.data);
-  const uint32_t n_tile = (len + 63) / 64;
+  const uint32_t n_tile = (s.len + 63) / 64;
 
   for (uint32_t tile = wave; tile < n_tile; tile += kSqWaves) {
     const uint32_t tile0 = tile * 64;
-    const uint32_t v     = tile0 + lane;
-    const bool valid     = v < len;
+    const bool valid     = tile0 + lane < s.len;
     f32x2_t accv[QPB / 2];
 #pragma unroll
     for (int j = 0; j < QPB / 2; ++j) accv[j] = f32x2_t{0.f, 0.f};
     float vn = 0.f;  // cosine: |v|^2 of this lane's decoded row
     const uint4* cp = data16 + ((g0 + tile) * a.n_chunks) * 64 + lane;
-    float bf[QPB];  // L2 early stop: the k-th bounds at the start of the tile (they only decrease)
+    float bf[QPB];  // L2 early stop: the k-th bounds at the start of the tile (they only decrease) - as in ivf_flat.hip
 #pragma unroll
     for (int j = 0; j < QPB; ++j) {
-      const uint32_t kk = __builtin_amdgcn_readfirstlane(kthb[j]);
-      bf[j] = (IP || j >= (int)item.count) ? -INFINITY : (kk >= 0xff800000u ? INFINITY : key_to_float(kk));
+      const uint32_t kk = __builtin_amdgcn_readfirstlane(s.kthb[j]);
+      bf[j] = (IP || j >= (int)s.item.count) ? -INFINITY : (kk >= 0xff800000u ? INFINITY : key_to_float(kk));
     }
     auto chunk_step = [&](const uint4& cw, const uint32_t ch) {
       const uint32_t words[4] = {cw.x, cw.y, cw.z, cw.w};
@@ -322,7 +273,7 @@ __global__ __launch_bounds__(kSqThreads) void ivf_sq_scan_kernel(sq_scan_args a)
         uint4 cws[kSqStop];  // padded rows of a tile are zero-filled: always readable
 #pragma unroll
         for (int c = 0; c < kSqStop; ++c) cws[c] = cp[(size_t)min(ch0 + (uint32_t)c, a.n_chunks - 1u) * 64];
-        sq_keep_loads_together(cws);
+        keep_loads_together(cws);
 #pragma unroll
         for (int c = 0; c < kSqStop; ++c) {
           const uint32_t ch = ch0 + (uint32_t)c;
@@ -356,135 +307,12 @@ __global__ __launch_bounds__(kSqThreads) void ivf_sq_scan_kernel(sq_scan_args a)
     }
 #pragma unroll
     for (int j = 0; j < QPB; ++j) {
-      if (j >= (int)item.count) break;
-      const float dj = METRIC == 1 ? -acc[j] : acc[j];  // smaller is better
-      if constexpr (ALL) {
-        bool keep = valid;
-        if (keep && a.filter_bits != nullptr) {
-          const int64_t sid = a.indices[(size_t)base_row + v];
-          keep              = (a.filter_bits[sid >> 5] >> (sid & 31)) & 1u;
-        }
-        const uint32_t p = pid[j];
-        if (keep) {
-          const size_t o  = (size_t)(p / a.n_probes) * a.scores_ld + a.pair_seg[p] + v;
-          a.all_scores[o] = dj;
-          a.all_rows[o]   = base_row + v;
-        }
-        continue;
-      }
-      const uint32_t bound = kthb[j];
-      unsigned long long m = __ballot(valid && float_to_key(dj) <= bound);
-      if (m == 0ull) continue;
-      const bool first = ((fresh >> j) & 1u) != 0u;
-      fresh &= ~(1u << j);
-      if (first && a.filter_bits == nullptr && __popcll(m) >= 12 && __ballot(dj != dj) == 0ull) {
-        // the wave's first candidates of query j: one sorting network instead of up to 64 serial insertions
-        const bool c = ((m >> lane) & 1ull) != 0ull;
-        float sd     = c ? dj : INFINITY;
-        uint32_t si  = c ? tile0 + (uint32_t)lane : 0xffffffffu;
-        wave_sort64(sd, si, lane);
-        top[j].d[0] = sd;
-        top[j].i[0] = si;
-        const float kd0 = top[j].rank_d(kr);
-        if (lane == 0 && kd0 < INFINITY) atomicMin(&kthb[j], float_to_key(kd0));
-        continue;
-      }
-      float kd      = top[j].rank_d(kr);
-      uint32_t ki   = top[j].rank_i(kr);
-      bool improved = false;
-      while (m != 0ull) {
-        const int src = (int)__ffsll((long long)m) - 1;
-        m &= m - 1ull;
-        const float cd    = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(dj), src));
-        const uint32_t ci = tile0 + (uint32_t)src;
-        if (a.filter_bits != nullptr) {
-          const int64_t sid = a.indices[(size_t)base_row + ci];
-          if (!((a.filter_bits[sid >> 5] >> (sid & 31)) & 1u)) continue;
-        }
-        if ((cd < kd) || (cd == kd && ci < ki)) {
-          top[j].insert(cd, ci, lane);
-          kd       = top[j].rank_d(kr);
-          ki       = top[j].rank_i(kr);
-          improved = true;
-        }
-      }
-      if (improved && lane == 0 && kd < INFINITY) atomicMin(&kthb[j], float_to_key(kd));
+      if (j >= (int)s.item.count) break;
+      list_scan_offer<QPB, E, ALL>(a, s, j, METRIC == 1 ? -acc[j] : acc[j], tile0, lane, tops);  // smaller is better
     }
   }
 
-  if constexpr (ALL) return;
-  // ---- merge the wave lists
-  __syncthreads();
-  if constexpr (E > 1) {
-    constexpr int KP2 = E == 2 ? 128 : 256;
-    float* sd    = reinterpret_cast<float*>(smem);
-    uint32_t* si = reinterpret_cast<uint32_t*>(smem + (size_t)kSqWaves * KP2 * 4);
-    for (int j = 0; j < QPB; ++j) {
-      if (j >= (int)item.count) break;  // workgroup-uniform
-#pragma unroll
-      for (int e = 0; e < E; ++e) {
-        const int r   = e * 64 + lane;
-        const bool in = r < (int)a.k;
-        sd[wave * KP2 + r] = in ? top[j].d[e] : INFINITY;
-        si[wave * KP2 + r] = in ? top[j].i[e] : 0xffffffffu;
-      }
-      __syncthreads();
-      merge_sorted_lists<kSqThreads>(sd, si, kSqWaves, KP2, tid);
-      const size_t o = (size_t)pid[j] * a.k;
-      for (int r = tid; r < (int)a.k; r += kSqThreads) {
-        const bool ok  = si[r] != 0xffffffffu;
-        a.out_d[o + r] = ok ? sd[r] : FLT_MAX;
-        a.out_i[o + r] = ok ? base_row + si[r] : 0xffffffffu;
-      }
-      if (tid == 0 && si[a.k - 1] != 0xffffffffu && sd[a.k - 1] < INFINITY)
-        atomicMin(&a.query_kth[pid[j] / a.n_probes], float_to_key(sd[a.k - 1]));
-      __syncthreads();  // the next query reuses the area
-    }
-    return;
-  }
-  float* mg_d    = reinterpret_cast<float*>(smem);
-  uint32_t* mg_i = reinterpret_cast<uint32_t*>(smem + (size_t)QPB * kSqWaves * a.k * 4);
-#pragma unroll
-  for (int j = 0; j < QPB; ++j) {
-    const int r = lane;
-    if (r < (int)a.k) {
-      mg_d[((size_t)j * kSqWaves + wave) * a.k + r] = top[j].d[0];
-      mg_i[((size_t)j * kSqWaves + wave) * a.k + r] = top[j].i[0];
-    }
-  }
-  __syncthreads();
-  if (wave < QPB && wave < (int)item.count) {
-    const int j = wave;
-    wave_top<1> fin;
-    fin.init();
-    float kd    = INFINITY;
-    uint32_t ki = 0xffffffffu;
-    const int n = kSqWaves * (int)a.k;
-    for (int b0 = 0; b0 < n; b0 += 64) {
-      float md    = INFINITY;
-      uint32_t mi = 0xffffffffu;
-      if (b0 + lane < n) { md = mg_d[(size_t)j * n + b0 + lane]; mi = mg_i[(size_t)j * n + b0 + lane]; }
-      unsigned long long m = __ballot(mi != 0xffffffffu && ((md < kd) || (md == kd && mi < ki)));
-      while (m != 0ull) {
-        const int src = (int)__ffsll((long long)m) - 1;
-        m &= m - 1ull;
-        const float cd    = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(md), src));
-        const uint32_t ci = __builtin_amdgcn_readlane(mi, src);
-        if ((cd < kd) || (cd == kd && ci < ki)) {
-          fin.insert(cd, ci, lane);
-          kd = fin.rank_d(kr);
-          ki = fin.rank_i(kr);
-        }
-      }
-    }
-    const size_t o = (size_t)pid[j] * a.k;
-    if (lane < (int)a.k) {
-      const bool ok     = fin.i[0] != 0xffffffffu;
-      a.out_d[o + lane] = ok ? fin.d[0] : FLT_MAX;
-      a.out_i[o + lane] = ok ? base_row + fin.i[0] : 0xffffffffu;
-    }
-    if (lane == 0 && kd < INFINITY) atomicMin(&a.query_kth[pid[j] / a.n_probes], float_to_key(kd));
-  }
+  if constexpr (!ALL) list_scan_merge<QPB, kSqWaves, E>(a, s, smem, tops);
 }
 
 __global__ void sq_postprocess_kernel(const uint32_t* __restrict__ pos, const float* __restrict__ d_in, int64_t n,
@@ -513,30 +341,13 @@ __global__ void sq_unpack_list_kernel(const uint8_t* __restrict__ data, uint32_t
   out[i] = data[(((size_t)(fr >> 6) * n_chunks + d / 16) * 64 + (size_t)(fr & 63)) * 16 + d % 16];
 }
 
-template <int E, int METRIC, bool ALL = false>
-void launch_sq_scan_kern(resources& res, const sq_scan_args& a, size_t smem, unsigned grid)
-{
-  auto kern = ivf_sq_scan_kernel<E, METRIC, ALL>;
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kSqThreads), smem, res.stream, a);
-}
-
 void launch_sq_scan(resources& res, const sq_scan_args& a, int metric_kind, size_t smem, unsigned grid, bool big_k)
 {
   profile_begin(res, "ivf_sq_scan_kernel");
-  if (a.all_scores != nullptr) {
-    if (metric_kind == 2)      launch_sq_scan_kern<1, 2, true>(res, a, smem, grid);
-    else if (metric_kind == 1) launch_sq_scan_kern<1, 1, true>(res, a, smem, grid);
-    else                       launch_sq_scan_kern<1, 0, true>(res, a, smem, grid);
-  } else if (big_k) {
-    if (metric_kind == 2)      launch_sq_scan_kern<4, 2>(res, a, smem, grid);
-    else if (metric_kind == 1) launch_sq_scan_kern<4, 1>(res, a, smem, grid);
-    else                       launch_sq_scan_kern<4, 0>(res, a, smem, grid);
-  } else {
-    if (metric_kind == 2)      launch_sq_scan_kern<1, 2>(res, a, smem, grid);
-    else if (metric_kind == 1) launch_sq_scan_kern<1, 1>(res, a, smem, grid);
-    else                       launch_sq_scan_kern<1, 0>(res, a, smem, grid);
-  }
+  list_scan_dispatch(a.all_scores != nullptr, big_k, metric_kind, [&](auto e, auto metric, auto all) {
+    list_scan_launch(res, ivf_sq_scan_kernel<decltype(e)::value, decltype(metric)::value, decltype(all)::value>, kSqThreads, a, smem,
+                     grid);
+  });
   profile_end(res, "ivf_sq_scan_kernel");
   HIP_TRY(hipGetLastError());
 }
@@ -659,7 +470,7 @@ void ivf_sq_search(resources& res, const ivf_sq_index& idx, uint32_t n_probes_in
   const uint32_t dim_pad  = idx.n_chunks * 16;
   const int metric_kind   = idx.metric == M_InnerProduct ? 1 : idx.metric == M_CosineExpanded ? 2 : 0;
   const bool cosm = idx.metric == M_CosineExpanded;
-  const size_t smem      = ((((size_t)qpb * kSqWaves * k_scan * 8) + 15) & ~size_t(15)) + 2 * 16 * 4;
+  const size_t smem      = list_scan_smem_bytes(qpb, kSqWaves, (uint32_t)k_scan);
   const size_t scores_ld = large_k ? largest_lists_total(idx.h_list_sizes, n_probes) : 0;
   int64_t max_batch = 1 << 15;
   {

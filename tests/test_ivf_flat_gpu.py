@@ -239,3 +239,110 @@ def test_inner_product_on_unnormalised_rows():
     assert oracle.recall(gi, ti) >= 0.4, oracle.recall(gi, ti)
     od, oi = oracle.ivf_flat_search(ex, q, 10, 8, metric="inner_product")
     assert (gi == oi).all() and (gd == od).all()
+
+
+# ------------------------------------------------------------------------------------------------ scan-kernel grid
+# The admission and merge code of the list scan (cuvs_amd/csrc/ivf_list_scan.hpp) through IVF-Flat's kernels: the edges of the
+# one-slot lists (k <= 64), the four-slot lists (k <= 256) and the non-fused path, every element type, planted ties, a filter.
+_DTYPES = {"f32": (np.float32, 1.0), "f16": (np.float16, 1.0), "i8": (np.int8, 1 / 128), "u8": (np.uint8, 1 / 256)}
+
+
+def _dup_data(n, d, nq, seed, dtype, dup):
+    x, q = _gen(n, d, nq, seed, dtype)
+    x[n - dup:] = x[:dup]  # duplicated rows: exact ties of every metric
+    q[:5] = x[:5]          # queries equal to (duplicated) rows
+    return x, q
+
+
+def _grid_cases():
+    ks = [1, 10, 64, 65, 256, 257]
+    names = list(_DTYPES)
+    out, n = [], 0
+    for metric in ("sqeuclidean", "euclidean", "inner_product", "cosine"):
+        for dim in (1, 3, 16, 17, 33, 128, 257):
+            if metric == "cosine" and dim == 1:
+                dim = 2
+            k, dt, filt = ks[n % len(ks)], names[n % len(names)], n % 2 == 1
+            out.append(pytest.param(metric, dim, k, dt, filt, id=f"{metric}-d{dim}-k{k}-{dt}{'-filter' if filt else ''}"))
+            n += 1
+    return out
+
+
+def _probe_ranks(ex, q, n_probes, metric, scale):
+    """[n_queries, n_lists] rank of every list among a query's probes (n_lists: not probed), from the oracle itself: the
+    index cut down to the first row of every list, its id the list number, searched with 1 .. n_probes probes"""
+    sizes = np.minimum(ex["list_sizes"], 1)
+    cut = dict(ex, list_sizes=sizes, rows=[r[:1] for r in ex["rows"]],
+               ids=[np.full(int(c), L, np.int64) for L, c in enumerate(sizes)])
+    rank = np.full((len(q), len(sizes)), len(sizes), np.int64)
+    for p in range(n_probes, 0, -1):  # a list probed with p probes has rank < p: the smallest such p - 1 stays
+        _, oi = oracle.ivf_flat_search(cut, q, p, p, metric=metric, coarse_scale=scale)
+        for r in range(len(q)):
+            rank[r, oi[r][oi[r] != np.iinfo(np.int64).max]] = p - 1
+    return rank
+
+
+def _oracle_filtered(ex, q, k, n_probes, metric, scale, keep, n):
+    """The oracle's ranking of every probed row (k = n: each once, ordered by (distance, flat row), then padding) with the
+    masked ids dropped, and the k best of it. Which rows of equal distance make it across the k-th place is decided as the
+    search decides it (ivf_common.hpp, oracle_ivf_flat.c): by probe rank, then by position in the list - with integer rows
+    such ties between rows of different lists are common. The winners keep the oracle's order."""
+    od, oi = oracle.ivf_flat_search(ex, q, n, n_probes, metric=metric, coarse_scale=scale)
+    rank = _probe_ranks(ex, q, n_probes, metric, scale)
+    list_of = np.empty(n, np.int64)
+    for L, ids in enumerate(ex["ids"]):
+        assert (np.diff(ids) > 0).all(), "in-list order is ascending id: ids stand in for the position in the list below"
+        list_of[ids] = L
+    wd = np.full((len(q), k), np.finfo(np.float32).max, np.float32)
+    wi = np.full((len(q), k), np.iinfo(np.int64).max, np.int64)
+    for r in range(len(q)):
+        found = oi[r] != np.iinfo(np.int64).max
+        pos = np.nonzero(found & keep[np.where(found, oi[r], 0)])[0]
+        d, ids = od[r, pos], oi[r, pos]
+        group = np.concatenate([[0], np.cumsum(d[1:] != d[:-1])])  # runs of equal distance, best first
+        sel = np.sort(np.lexsort((ids, rank[r, list_of[ids]], group))[:k])  # (in-list order is ascending id)
+        wd[r, :len(sel)], wi[r, :len(sel)] = d[sel], ids[sel]
+    return wd, wi
+
+
+@pytest.mark.parametrize("metric,dim,k,dt,filt", _grid_cases())
+def test_search_parity_grid(metric, dim, k, dt, filt):
+    import torch
+    from cuvs_amd._lib import BITSET
+    from cuvs_amd.neighbors import ivf_flat
+
+    n, n_lists, n_probes, nq = 4000, 20, 6, 60
+    dtype, scale = _DTYPES[dt]
+    x, q = _dup_data(n, dim, nq, 100 + dim, dtype, 400)
+    index = _build(x, n_lists=n_lists, metric=metric, kmeans_n_iters=10)
+    ex = ivf_flat.export_for_oracle(index, dtype)
+    if filt:
+        keep = np.random.default_rng(dim).random(n) < 0.7
+        bits = np.zeros((n + 31) // 32, np.uint32)
+        np.bitwise_or.at(bits, np.nonzero(keep)[0] >> 5, (np.uint32(1) << (np.nonzero(keep)[0] & 31).astype(np.uint32)))
+        gd, gi = ivf_flat.search(ivf_flat.SearchParams(n_probes=n_probes), index, torch.from_numpy(q).cuda(), k,
+                                 filter=(torch.from_numpy(bits.view(np.int32)).cuda(), BITSET))
+        torch.cuda.synchronize()
+        gd, gi = gd.cpu().numpy(), gi.cpu().numpy()
+        wd, wi = _oracle_filtered(ex, q, k, n_probes, metric, scale, keep, n)
+    else:
+        gd, gi = _search(index, q, k, n_probes)
+        wd, wi = oracle.ivf_flat_search(ex, q, k, n_probes, metric=metric, coarse_scale=scale)
+    assert np.array_equal(gi, wi), f"ids differ in {np.count_nonzero((gi != wi).any(1))} rows"
+    assert np.array_equal(gd.view(np.uint32), wd.view(np.uint32)), "distances differ"
+
+
+@pytest.mark.parametrize("dt", ["f32", "i8"])
+def test_search_many_probes_two_phase(dt):
+    """n_probes > 8 (L2: the nearest list of every query is scanned first) with fewer than 256 queries, which keeps the
+    matrix-core tail phase out: head and tail both run on the scan kernel, with several work items per list"""
+    from cuvs_amd.neighbors import ivf_flat
+
+    dtype, scale = _DTYPES[dt]
+    x, q = _dup_data(6000, 40, 200, 5, dtype, 300)
+    index = _build(x, n_lists=24, kmeans_n_iters=10)
+    ex = ivf_flat.export_for_oracle(index, dtype)
+    for k in (10, 100):
+        gd, gi = _search(index, q, k, 12)
+        wd, wi = oracle.ivf_flat_search(ex, q, k, 12, coarse_scale=scale)
+        assert np.array_equal(gi, wi) and np.array_equal(gd.view(np.uint32), wd.view(np.uint32)), k
