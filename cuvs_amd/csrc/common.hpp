@@ -86,6 +86,7 @@ struct tuning {
   int pq_head_rows      = -1;  // CUVS_AMD_PQ_HEAD_ROWS: rows of a query's nearest list the head phase scores exactly for its bound (the rest of
                                // that list goes through the filter like any other probe); 0: the whole list (rounds 3-4); -1: default rule
   int pq_overlap        = 1;   // CUVS_AMD_PQ_OVERLAP=0: the IVF-PQ batch on one stream (rounds 1-4; comparator of the two-stream schedule)
+  int pq_unit_order     = 2;   // CUVS_AMD_PQ_UNIT_ORDER: hand-out order of the matrix-core filter's work units (pq3_tail). 0: list order, every XCD a contiguous eighth (comparator); 1: by cost, largest first; 2: list order, the cheapest units worth an eighth of the cost last, largest of those first; 1 and 2 stride the XCD shares over the array
   int coarse_grouped    = 1;   // CUVS_AMD_COARSE_GROUPED=0: coarse search through the plain distance matrix + select_k (rounds 1-4; comparator)
   int pq_filter4        = 1;   // CUVS_AMD_PQ_FILTER4=0: the matrix-core filter of round 3 (two waves per SIMD, 64-query units; comparator)
   int flat_scan3        = 1;   // CUVS_AMD_FLAT_SCAN3=0: IVF-Flat tail phase on the scan kernel (comparator in the tests)

@@ -155,7 +155,8 @@ struct filter4_params {
   uint2* surv;         // n_chunks x kSurvChunk entries
   uint32_t* surv_cnt;  // [1] chunks handed out so far (may run past n_chunks)
   uint32_t n_chunks, n_probes, unit_rows;
-  unsigned long long* stats;  // optional [8] as in pq_filter_kernel
+  unsigned long long* stats;  // optional [kPq3Stats]: [0, 8) as in pq_filter_kernel, the rest see pq_filter4_kernel
+  uint32_t strided;           // the units are in cost order: ticket t of XCD x is position 8 t + x (unit_position)
 };
 
 // LDS byte address of a decode-table entry in ONE instruction: the low word of `addr` becomes (byte BYTE of w) << two (the
@@ -179,7 +180,10 @@ typedef __attribute__((address_space(3))) const uint32_t lds_u32_t;
 // TERM: L2 (the rows' terms are the accumulators' initial values); inner product starts from zero
 // DBG: ablations (timing only, wrong results): 1 conflict-free gathers, 2 no gathers, 4 no MFMAs, 8 no code loads
 // STATS: the counters / cycle stamps of CUVS_AMD_SCAN_DEBUG=1024 (s_memtime is a scalar memory operation: in the subtile
-// loop it would make every wait on the gathers a wait for everything)
+// loop it would make every wait on the gathers a wait for everything). Beyond pq_filter_kernel's eight: [8 + g] wave cycles
+// in the subtile loop of the units with g + 1 query groups and [12 + g] their subtiles; how the kernel ENDS, from the
+// constant-rate counter that all CUs share, per wave from its first ticket to the end of its last unit: [16] first start,
+// [17] last end, [18] sum of (end - start), [19] waves. (No stamp of these is in the production instantiation.)
 // PL: pq_len (1, 2, 4, 8): a code byte stands for PL fp16 values - the lane's 8 K elements of an MFMA step are 8 / PL
 // codebook entries of 2 PL bytes; the 8 code bytes a lane holds of a chunk feed PL consecutive K steps
 // PC: PER_CLUSTER codebooks - one decode table of 256 entries per LIST, shared by its subspaces: every wave keeps the table
@@ -209,13 +213,16 @@ __global__ __launch_bounds__(kF4Threads) void pq_filter4_kernel(const filter4_pa
 
   const uint32_t lane = threadIdx.x & 63u, ql = lane & 31u, h = lane >> 5;
   const uint32_t n_units = *a.n_units;
-  const uint32_t chunk   = (n_units + 7u) / 8u;
+  const bool strided     = a.strided != 0u;
   const uint32_t s_base  = a.pair_off[a.n_lists];
   uint32_t xcd = blockIdx.x & 7u, hops = 0u;
   const uint32_t two = PL == 1 ? 1u : PL == 2 ? 2u : PL == 4 ? 3u : 4u;  // log2(kEntry)
   const uint32_t lane_code_off = ql * 16u + h * 8u, lane_term_off = h * 16u;  // byte offsets of this lane inside a subtile
 
   unsigned long long st_pairs = 0, st_surv = 0, st_sub = 0, st_slow = 0, st_units = 0, st_t[3] = {0, 0, 0};
+  unsigned long long st_ng_t[4] = {0, 0, 0, 0}, st_ng_sub[4] = {0, 0, 0, 0};
+  const unsigned long long w_start = STATS ? wall_clock64() : 0ull;
+  unsigned long long w_end = w_start;
   // ---- unit pipeline: the ticket of the NEXT unit is drawn when a unit starts and its descriptor is loaded a few
   // subtiles later, so that a unit's prologue is ONE memory round trip (B operands, codes and terms together) instead
   // of a chain of five (ticket -> descriptor -> list offsets -> operands -> codes)
@@ -227,11 +234,10 @@ __global__ __launch_bounds__(kF4Threads) void pq_filter4_kernel(const filter4_pa
     if (lane == 0) tk_v = atomicAdd(a.xcd_ticket + xcd * 32, 1u);
   };
   auto load_desc = [&]() {  // resolves the pending ticket; false: this XCD's share has run dry
-    const uint32_t share0 = min(n_units, xcd * chunk), share_len = min(chunk, n_units - share0);
     const uint32_t t = __builtin_amdgcn_readfirstlane(tk_v);
-    desc_ok = t < share_len;
+    desc_ok = t < unit_share_len(n_units, xcd, strided);
     if (desc_ok) {
-      const filter_unit* up = a.units + share0 + t;
+      const filter_unit* up = a.units + unit_position(n_units, xcd, t, strided);
       d0 = *reinterpret_cast<const uint4*>(up);
       d1 = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(up) + 16);
     }
@@ -530,6 +536,11 @@ __global__ __launch_bounds__(kF4Threads) void pq_filter4_kernel(const filter4_pa
       st_t[0] += t_loop - t_unit;  // unit prologue (B operands, first decode)
       st_t[1] += t_end - t_loop;   // subtile loop
       st_units += 1u;
+      if (u0 < u1) {
+        const uint32_t gi = min((count + 31u) >> 5, (uint32_t)NGM) - 1u;
+        st_ng_t[gi] += t_end - t_loop; st_ng_sub[gi] += u1 - u0;
+      }
+      w_end = wall_clock64();
     }
   }
   if (STATS && lane == 0) {
@@ -537,6 +548,9 @@ __global__ __launch_bounds__(kF4Threads) void pq_filter4_kernel(const filter4_pa
     atomicAdd(&a.stats[0], st_pairs); atomicAdd(&a.stats[2], st_sub);
     atomicAdd(&a.stats[3], st_slow);  atomicAdd(&a.stats[4], st_t[0]); atomicAdd(&a.stats[5], st_t[1]);
     atomicAdd(&a.stats[6], st_t[2]);  atomicAdd(&a.stats[7], st_units);
+    for (int g = 0; g < 4; ++g) { atomicAdd(&a.stats[8 + g], st_ng_t[g]); atomicAdd(&a.stats[12 + g], st_ng_sub[g]); }
+    atomicMin(&a.stats[16], w_start); atomicMax(&a.stats[17], w_end);
+    atomicAdd(&a.stats[18], w_end - w_start); atomicAdd(&a.stats[19], 1ull);
   }
   if (s_chunk < a.n_chunks)
     for (uint32_t i = s_fill + lane; i < kSurvChunk; i += 64u) a.surv[(size_t)s_chunk * kSurvChunk + i] = make_uint2(0xffffffffu, 0u);
@@ -590,7 +604,7 @@ void pq4_filter(resources& res, const filter4_launch& l)
   g.n_lists = l.n_lists; g.bq = b.bq; g.thr = l.thr; g.cb16 = l.cb16; g.codes = l.codes; g.list_offsets = l.list_offsets;
   g.list_sizes = l.list_sizes; g.row_term = l.row_term; g.qflag = l.qflag; g.surv = static_cast<uint2*>(l.surv);
   g.surv_cnt = l.surv_cnt; g.n_chunks = l.surv_entries / kSurvChunk; g.n_probes = l.n_probes; g.unit_rows = l.unit_rows;
-  g.stats = l.stats;
+  g.stats = l.stats; g.strided = l.strided != 0 ? 1u : 0u;
   // the two K halves of the decode table lie 64 KiB apart; PER_CLUSTER: a 4 KiB table region per wave
   const size_t fsmem = l.per_cluster ? 4 * 4096 : 65536 + (size_t)l.nch * 8 * 512 * l.pl;
   const bool term = l.row_term != nullptr;
@@ -613,6 +627,7 @@ void pq4_filter(resources& res, const filter4_launch& l)
       case 81: launch(pq_filter4_kernel<4, 2, true, 81>); break;
       default:
         if (l.stats != nullptr && term) launch(pq_filter4_kernel<4, 2, true, 0, true>);
+        else if (l.stats != nullptr) launch(pq_filter4_kernel<4, 2, false, 0, true>);
         else if (term) launch(pq_filter4_kernel<4, 2, true, 0>);
         else launch(pq_filter4_kernel<4, 2, false, 0>);
         break;
@@ -624,6 +639,9 @@ void pq4_filter(resources& res, const filter4_launch& l)
     if (l.per_cluster) {
       if (term) launch(pq_filter4_kernel<N, P, true, 0, false, true>); else launch(pq_filter4_kernel<N, P, false, 0, false, true>);
     } else {
+      if constexpr (P == 2 && N <= 4) {  // (the counters of CUVS_AMD_SCAN_DEBUG=1024 at the small shapes of the tests)
+        if (l.stats != nullptr && term) { launch(pq_filter4_kernel<N, P, true, 0, true>); return; }
+      }
       if (term) launch(pq_filter4_kernel<N, P, true, 0>); else launch(pq_filter4_kernel<N, P, false, 0>);
     }
   };

@@ -18,6 +18,42 @@ struct filter_unit {
   uint32_t pad0, pad1;
 };
 
+// ---- hand-out order of the units (pq3_tail: order_units_kernel; pq_filter4_kernel and pq_filter_kernel read it)
+// The waves draw units greedily, so a kernel ends about one unit after the queue runs dry: the units are handed out with the
+// cheap ones LAST. Cost key of a unit: its 32-row subtiles x the cost of a subtile at its number of 32-query groups, scaled to
+// [1, kUnitKeys) (unit_rows: the longest row chunk of the launch); 0 for a unit without rows - the key that is placed last.
+// Non-decreasing in rows and in groups. Weights: wave cycles per subtile of pq_filter4_kernel at the bench shape, in units of
+// 16 cycles - 806 / 1015 / 1287 / 1690 at 1 / 2 / 3 / 4 groups (profiles/unit_order_step0.txt; the model's first guess was
+// 2 + groups, i.e. 3 : 4 : 5 : 6 - the measured ratio is 3 : 3.8 : 4.8 : 6.3).
+constexpr uint32_t kUnitKeys = 512u;
+__host__ __device__ inline uint32_t unit_group_weight(const uint32_t ng)
+{
+  return ng <= 1u ? 50u : ng == 2u ? 63u : ng == 3u ? 80u : 106u;
+}
+__host__ __device__ inline uint32_t unit_cost_key(const uint32_t rows, const uint32_t ng, const uint32_t unit_rows)
+{
+  if (rows == 0u) return 0u;
+  const uint64_t cost = (uint64_t)((rows + 31u) >> 5) * unit_group_weight(ng);
+  const uint64_t cmax = (uint64_t)(((unit_rows > rows ? unit_rows : rows) + 31u) >> 5) * unit_group_weight(4u);
+  const uint64_t k    = 1u + cost * (kUnitKeys - 2u) / cmax;
+  return (uint32_t)(k < kUnitKeys - 1u ? k : kUnitKeys - 1u);
+}
+// Ticket t of XCD x -> position in the unit array. Contiguous (list order, CUVS_AMD_PQ_UNIT_ORDER=0): XCD x owns the x-th
+// eighth - the units of a list run on one XCD. Strided (the cost order): position 8 t + x - every XCD's share has the
+// array's cost profile and ends on its cheap units. t < unit_share_len() or the share has run dry.
+__host__ __device__ inline uint32_t unit_share_len(const uint32_t n_units, const uint32_t xcd, const bool strided)
+{
+  if (strided) return (n_units - xcd + 7u) / 8u;  // (n_units + 7 >= xcd: no wrap)
+  const uint32_t chunk = (n_units + 7u) / 8u, share0 = n_units < xcd * chunk ? n_units : xcd * chunk;
+  return chunk < n_units - share0 ? chunk : n_units - share0;
+}
+__host__ __device__ inline uint32_t unit_position(const uint32_t n_units, const uint32_t xcd, const uint32_t t, const bool strided)
+{
+  if (strided) return 8u * t + xcd;
+  const uint32_t chunk = (n_units + 7u) / 8u, share0 = n_units < xcd * chunk ? n_units : xcd * chunk;
+  return share0 + t;
+}
+
 // Largest value B with: exact score > bound  whenever  (row term - 2 dot16 / sc^2) > B   (L2; see the file header).
 // With T the real-valued score, S the score in the reference's arithmetic and A the filter's value
 //   S >= T (1 - eps) - alpha                          entry roundings of the LUT type, summation in the score type
@@ -88,6 +124,7 @@ struct filter4_launch {
   int flat = 0;               // IVF-Flat's pairs (an unserved query survives everything instead of being handed back)
   int bprep_only = 0;         // the pre-pass alone (B operands + thresholds): IVF-Flat's flat_filter2_kernel follows it
   int head_labels = 0;        // the pre-pass over the HEAD pairs (labels [0, n_lists)) instead of the tail pairs: IVF-Flat's bound-only head phase
+  int strided = 0;            // the units are in cost order: tickets map to strided positions (unit_position)
 };
 void pq4_filter(resources& res, const filter4_launch& l);
 

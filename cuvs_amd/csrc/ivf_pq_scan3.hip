@@ -203,6 +203,140 @@ __global__ void fill_units_kernel(const uint32_t* __restrict__ pair_off, uint32_
   for (; w < w_end; ++w) units[w] = filter_unit{L, b, 1u, 0u, base, 0u, 0u, 0u};
 }
 
+// ------------------------------------------------------------------ hand-out order of the units (ivf_pq_filter_common.hpp)
+// `out` = the units of `in` (list order) in hand-out order, the descriptors themselves: a unit's prologue stays one memory
+// round trip. order 1: by cost key, largest first; order 2: list order, but the cheapest units - those whose keys lie below the
+// largest K with (cost of all keys < K) <= an eighth of the total - follow at the end, largest of those first. Units of equal
+// key keep list order, so the array is the same on every run. A stable counting sort in ONE workgroup (~20 k units at the bench
+// shape): wave w owns the w-th eighth of the array and a row of counters; pass 1 counts by key, one block scan turns the
+// counts into first positions (class major - list-order part, then keys downwards - wave minor), pass 2 places: the lanes of a
+// wave that hold the same class find each other by ballots and take consecutive positions.
+// The workgroup has the footprint of one of the head kernel's (512 threads, at most 80 registers, less LDS): in the two-stream
+// schedule it starts as soon as ONE head workgroup retires (1024 threads at 100 registers waited up to 0.3 ms for a CU).
+constexpr uint32_t kOrdWaves = 8u, kOrdThreads = 64u * kOrdWaves;
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6, 8))) void order_units_kernel(const filter_unit* __restrict__ in, const uint32_t* __restrict__ n_units,
+                                                           filter_unit* __restrict__ out, uint32_t unit_rows, int order)
+{
+  __shared__ uint32_t cnt[kOrdWaves][kUnitKeys];  // pass 1: units of (wave, key); pass 2: next position of (wave, key)
+  __shared__ uint32_t head_pos[kOrdWaves];        // the same for the list-order part (keys >= k_star)
+  __shared__ int scan_smem[17];
+  __shared__ uint32_t k_star_s;
+  const uint32_t n = *n_units;
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  const uint32_t per = (n + kOrdWaves * 64u - 1u) / (kOrdWaves * 64u) * 64u;  // units per wave
+  const uint32_t b = min(n, w * per), e = min(n, b + per);
+  for (uint32_t i = threadIdx.x; i < kOrdWaves * kUnitKeys; i += kOrdThreads) (&cnt[0][0])[i] = 0u;
+  if (threadIdx.x == 0) k_star_s = order == 1 ? kUnitKeys : 0u;
+  __syncthreads();
+  auto key_of = [&](const uint4 d0, const uint2 d1) {  // (list, first, count, row0), (base_row, r_end)
+    return unit_cost_key(d1.y > d0.w ? d1.y - d0.w : 0u, (d0.z + 31u) >> 5, unit_rows);
+  };
+  // (the kernel runs next to the head kernel, where a dependent load takes microseconds: the descriptors of kOrdAhead
+  // steps are requested before the first is used, in both passes)
+  constexpr uint32_t kOrdAhead = 4u;
+  static_assert(kUnitKeys <= kOrdThreads, "a thread per key in the scan of the costs");
+  for (uint32_t i0 = b; i0 < e; i0 += 64u * kOrdAhead) {  // (wave-uniform)
+    uint4 d0[kOrdAhead];
+    uint2 d1[kOrdAhead];
+#pragma unroll
+    for (uint32_t j = 0; j < kOrdAhead; ++j) {
+      const uint32_t i = min(i0 + j * 64u + lane, e - 1u);
+      d0[j] = *reinterpret_cast<const uint4*>(in + i);
+      d1[j] = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(in + i) + 16);
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < kOrdAhead; ++j)
+      if (i0 + j * 64u + lane < e) atomicAdd(&cnt[w][key_of(d0[j], d1[j])], 1u);
+  }
+  __syncthreads();
+  {  // order 2: k_star (sums in int: up to 2^21 units; beyond, the array stays in list order)
+    int v = 0;
+    if (threadIdx.x < kUnitKeys)
+      for (uint32_t ww = 0; ww < kOrdWaves; ++ww) v += (int)(cnt[ww][threadIdx.x] * threadIdx.x);
+    if (n > (1u << 21)) v = 0;
+    int total;
+    const int below = block_exclusive_scan(v, scan_smem, &total);  // cost of the keys < threadIdx.x
+    if (order == 2 && n <= (1u << 21) && threadIdx.x < kUnitKeys && (long long)below * 8 <= (long long)total)
+      atomicMax(&k_star_s, threadIdx.x);
+    __syncthreads();
+  }
+  const uint32_t k_star = k_star_s;
+  {  // a wave's units of the list-order part
+    uint32_t s = 0;
+    for (uint32_t key = lane; key < kUnitKeys; key += 64u) s += key >= k_star ? cnt[w][key] : 0u;
+    for (uint32_t o = 32u; o > 0u; o >>= 1) s += __shfl_xor(s, o);
+    if (lane == 0) head_pos[w] = s;
+  }
+  __syncthreads();
+  {  // counts -> first positions; entry s of the sequence: the list-order part of wave s, then (key kUnitKeys - 1 - c, wave ww)
+    constexpr uint32_t kPer = (kOrdWaves + kOrdWaves * kUnitKeys + kOrdThreads - 1u) / kOrdThreads;
+    uint32_t vals[kPer];
+    int sum = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < kPer; ++j) {
+      const uint32_t s = threadIdx.x * kPer + j;
+      uint32_t v = 0u;
+      if (s < kOrdWaves) v = head_pos[s];
+      else if (s < kOrdWaves + kOrdWaves * kUnitKeys) {
+        const uint32_t key = kUnitKeys - 1u - (s - kOrdWaves) / kOrdWaves, ww = (s - kOrdWaves) % kOrdWaves;
+        v = key < k_star ? cnt[ww][key] : 0u;
+      }
+      vals[j] = v;
+      sum += (int)v;
+    }
+    int total;
+    uint32_t run = (uint32_t)block_exclusive_scan(sum, scan_smem, &total);
+#pragma unroll
+    for (uint32_t j = 0; j < kPer; ++j) {
+      const uint32_t s = threadIdx.x * kPer + j;
+      if (s < kOrdWaves) head_pos[s] = run;
+      else if (s < kOrdWaves + kOrdWaves * kUnitKeys) {
+        const uint32_t key = kUnitKeys - 1u - (s - kOrdWaves) / kOrdWaves, ww = (s - kOrdWaves) % kOrdWaves;
+        if (key < k_star) cnt[ww][key] = run;
+      }
+      run += vals[j];
+    }
+  }
+  __syncthreads();
+  volatile uint32_t* my_pos  = cnt[w];
+  volatile uint32_t* my_head = head_pos + w;
+  for (uint32_t i0 = b; i0 < e; i0 += 64u * kOrdAhead) {  // (wave-uniform)
+    uint4 a0[kOrdAhead], a1[kOrdAhead];
+#pragma unroll
+    for (uint32_t j = 0; j < kOrdAhead; ++j) {
+      const uint32_t i = min(i0 + j * 64u + lane, e - 1u);
+      a0[j] = reinterpret_cast<const uint4*>(in + i)[0];
+      a1[j] = reinterpret_cast<const uint4*>(in + i)[1];
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < kOrdAhead; ++j) {
+      const uint4 d0 = a0[j], d1 = a1[j];
+      const bool valid = i0 + j * 64u + lane < e;
+      const uint32_t key = key_of(d0, make_uint2(d1.x, d1.y));
+      const uint32_t cls = !valid ? 2u * kUnitKeys - 1u : key >= k_star ? kUnitKeys : key;  // (kUnitKeys: the list-order part)
+      unsigned long long peers = ~0ull;  // the lanes of the same class
+#pragma unroll
+      for (uint32_t bit = 0; (1u << bit) < 2u * kUnitKeys; ++bit) {
+        const bool mine = ((cls >> bit) & 1u) != 0u;
+        const unsigned long long m = __ballot(mine);
+        peers &= mine ? m : ~m;
+      }
+      const uint32_t rank = (uint32_t)__popcll(peers & ((1ull << lane) - 1ull)), same = (uint32_t)__popcll(peers);
+      uint32_t base = 0u;
+      if (valid) base = cls == kUnitKeys ? *my_head : my_pos[key];
+      __builtin_amdgcn_wave_barrier();  // (every lane has read its class' position before the first of the class moves it on)
+      if (valid && rank == 0u) {
+        if (cls == kUnitKeys) *my_head = base + same; else my_pos[key] = base + same;
+      }
+      __builtin_amdgcn_wave_barrier();
+      if (valid) {
+        reinterpret_cast<uint4*>(out + base + rank)[0] = d0;
+        reinterpret_cast<uint4*>(out + base + rank)[1] = d1;
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------------ the filter
 struct filter_params {
   const filter_unit* units;
@@ -246,6 +380,7 @@ struct filter_params {
   // xbuf[pair position][row of the list], ldx floats per pair; lbase: first label of the pairs served (0: head pairs)
   float* xbuf;
   uint32_t ldx, lbase;
+  uint32_t strided;  // pq_filter_kernel: the units are in cost order, ticket t of XCD x is position 8 t + x (unit_position)
 };
 
 // NCH: 16-byte code chunks per row = pq_dim / 16 (pq_len 2: rot_dim = 32 NCH, 2 NCH MFMA K steps). Up to 4 chunks a
@@ -274,24 +409,24 @@ __global__ __launch_bounds__(kFThreads) void pq_filter_kernel(const filter_param
   // XCD x owns the x-th eighth of the (list-sorted) unit array; its waves draw units through one ticket counter (the
   // units of a list run on one XCD at about the same time and share its L2). A wave whose XCD has run dry moves on to
   // the next XCD's share: the shares are equal in units, not in work.
+  // (units in cost order, pq3_tail: the shares are strided - unit_position)
   const uint32_t n_units = *a.n_units;
-  const uint32_t chunk = (n_units + 7u) / 8u;
+  const bool strided = a.strided != 0u;
   uint32_t xcd = blockIdx.x & 7u, hops = 0u;
   const uint4* codes16 = reinterpret_cast<const uint4*>(a.codes);
 
   unsigned long long st_pairs = 0, st_surv = 0, st_sub = 0, st_slow = 0, st_units = 0, st_t[3] = {0, 0, 0};
   for (;;) {
-    const uint32_t share0 = min(n_units, xcd * chunk), share_len = min(chunk, n_units - share0);
-    const filter_unit* share = a.units + share0;
     uint32_t t = 0;
     if (lane == 0) t = atomicAdd(a.xcd_ticket + xcd * 32, 1u);
     t = __builtin_amdgcn_readfirstlane(t);
-    if (t >= share_len) {
+    if (t >= unit_share_len(n_units, xcd, strided)) {
       if (++hops == 8u) break;
       xcd = (xcd + 1u) & 7u;
       continue;
     }
-    const uint4 uu = *reinterpret_cast<const uint4*>(share + t);
+    const filter_unit* const unit = a.units + unit_position(n_units, xcd, t, strided);
+    const uint4 uu = *reinterpret_cast<const uint4*>(unit);
     const uint32_t L = __builtin_amdgcn_readfirstlane(uu.x), first = __builtin_amdgcn_readfirstlane(uu.y),
                    count = __builtin_amdgcn_readfirstlane(uu.z), row0 = __builtin_amdgcn_readfirstlane(uu.w);
     const uint32_t base_row = a.list_offsets[L], len = a.list_sizes[L];
@@ -359,7 +494,7 @@ __global__ __launch_bounds__(kFThreads) void pq_filter_kernel(const filter_param
     // ---- rows of the unit, 32 at a time. Software pipeline of a wave: the code words are loaded two subtiles ahead;
     // the 32 gathers that decode subtile u + 1 are issued right after the MFMAs of subtile u and land while its
     // accumulators are screened; the other wave of the SIMD fills the matrix pipe meanwhile.
-    const uint32_t r_end = __builtin_amdgcn_readfirstlane(share[t].r_end);
+    const uint32_t r_end = __builtin_amdgcn_readfirstlane(unit->r_end);
     const uint32_t u0 = row0 >> 5, u1 = (r_end + 31u) >> 5;
     auto load_codes = [&](const uint32_t u, uint2 (&cw)[NCH]) {
       const uint32_t fr = base_row + (min(u, u1 - 1u) << 5) + ql;  // this lane's row (padded rows of a group are readable)
@@ -2769,8 +2904,16 @@ void pq3_tail(resources& res, const ivf_pq_index& idx, const pq3_run& r)
     hipLaunchKernelGGL(fill_units_kernel, dim3(grid_blocks(idx.n_lists, 256)), dim3(256), 0, res.stream, r.pair_off, idx.n_lists,
                        idx.list_offsets.data(), idx.list_sizes.data(), r.unit_rows, r.unit_off, units, group, idx.n_lists);
   }
+  // the hand-out order (two-stream schedule: on the helper stream, which ends well before the head kernel does)
+  const bool ordered = r.unit_order != 0 && r.units_ord != nullptr;
+  if (ordered) {
+    if (r.stage != 2)
+      hipLaunchKernelGGL(order_units_kernel, dim3(1), dim3(kOrdThreads), 0, res.stream, units, r.unit_off + idx.n_lists,
+                         static_cast<filter_unit*>(r.units_ord), r.unit_rows, r.unit_order);
+    units = static_cast<filter_unit*>(r.units_ord);
+  }
   filter_params f{};
-  f.units = units; f.n_units = r.unit_off + idx.n_lists; f.xcd_ticket = r.xcd_ticket;
+  f.units = units; f.n_units = r.unit_off + idx.n_lists; f.xcd_ticket = r.xcd_ticket; f.strided = ordered ? 1u : 0u;
   f.sorted_pairs = r.sorted_pairs; f.rot_queries = r.rot_queries; f.centers_rot = idx.centers_rot.data();
   uint32_t nch8 = 0;
   const uint8_t* codes8 = pq3_codes(res, idx, &nch8);
@@ -2810,7 +2953,7 @@ void pq3_tail(resources& res, const ivf_pq_index& idx, const pq3_run& r)
     l.cbmax = f.cbmax; l.dmax = f.dmax; l.bound_max = f.bound_max; l.is_ip = r.is_ip; l.dbg = r.filter_dbg; l.nch = nch;
     l.pl = (int)idx.pq_len; l.per_cluster = idx.codebook_kind != 0 ? 1 : 0;
     l.n_pairs = r.nq * (int64_t)r.n_probes; l.stats = r.stats; l.grid = grid;
-    l.stage = r.stage; l.pair_norms = r.pair_norms;
+    l.stage = r.stage; l.pair_norms = r.pair_norms; l.strided = ordered ? 1 : 0;
     pq4_filter(res, l);
     if (r.stage == 1) return;  // (the helper stream's share: units, B operands, norms)
   } else {
@@ -3467,3 +3610,15 @@ void pq3_merge(resources& res, const pq3_run& r, float* top_d, uint32_t* top_i)
 }
 
 }  // namespace cuvs_amd
+
+// Test hook (no reference counterpart; tests/test_pq_unit_order_cpu.py) over the two host + device functions of the unit
+// hand-out that pq_filter4_kernel, pq_filter_kernel and order_units_kernel share: out = {cost key of a unit of `rows` rows and
+// `groups` query groups at row chunks of up to `unit_rows`, units of XCD `xcd`'s share of `n_units`, position of its ticket `t`}.
+extern "C" __attribute__((visibility("default"))) void cuvsAmdIvfPqUnitOrderHook(uint32_t rows, uint32_t groups, uint32_t unit_rows,
+                                                                                 uint32_t n_units, uint32_t xcd, uint32_t t,
+                                                                                 int strided, uint32_t out[3])
+{
+  out[0] = cuvs_amd::unit_cost_key(rows, groups, unit_rows);
+  out[1] = cuvs_amd::unit_share_len(n_units, xcd, strided != 0);
+  out[2] = cuvs_amd::unit_position(n_units, xcd, t, strided != 0);
+}

@@ -10,6 +10,8 @@ struct pq3_tables {
   float sc, cbmax, dmax;
 };
 
+constexpr int kPq3Stats = 24;  // words of pq3_run::stats (pq_filter4_kernel's STATS build writes 20, the other filters 8)
+
 // one batch of the tail phase; all pointers device memory owned by the caller (ivf_pq_search)
 struct pq3_run {
   int64_t nq;
@@ -38,6 +40,11 @@ struct pq3_run {
   void* units;                   // work units of the filter, pq3_max_units() entries
   uint32_t* unit_off;            // [n_lists + 1]
   uint32_t unit_rows;
+  // hand-out order of the units (pq3_tail only): 0 list order, XCD shares contiguous; 1 by cost, largest first; 2 list order,
+  // the cheapest units worth an eighth of the cost at the end, largest of those first - 1 and 2 need units_ord, a second
+  // array of pq3_max_units() entries that receives the ordered copy (the filter reads that one, strided over the XCDs)
+  int unit_order = 0;
+  void* units_ord = nullptr;
   uint32_t* xcd_ticket;          // 8 x 32 zeroed words
   void* fb_items;                // work_item[n tail pairs]: single-pair items of the flagged queries
   const uint32_t* filter_bits;
@@ -45,7 +52,7 @@ struct pq3_run {
   void* bq;                      // pq_filter4_kernel: [tail pairs] x rot_dim fp16 B operands (nullptr: pq_filter_kernel, two waves per SIMD)
   float* thr;                    //   and [tail pairs] thresholds, both written by the pre-pass
   int filter_dbg;                // ablation bits of the filter kernel (timing only)
-  unsigned long long* stats;     // optional device [8]
+  unsigned long long* stats;     // optional device [kPq3Stats], zeroed, word 16 (a minimum) all ones
   // Two-stream schedule of a batch (ivf_pq_search.hip, round 5): everything of the tail phase that does not depend on the head
   // phase's bounds - work units, B operands - runs on a helper stream WHILE the head kernel runs.
   //   stage 0: the whole tail phase on one stream (every shape outside the two-stream schedule)

@@ -2262,7 +2262,8 @@ struct pq_search_scratch {
     query_kth = dev_buf<uint32_t>(res, bs); tickets = dev_buf<uint32_t>(res, 4 * 8 * 32);
     cand_r = dev_buf<uint32_t>(res, mc ? np * k : 0); qstate = dev_buf<uint32_t>(res, mc ? 4 * bs + 8 + pq3_regions(res) : 0);
     unit_off = dev_buf<uint32_t>(res, mc ? nl + 1 : 0); surv = dev_buf<uint2>(res, pl.surv_cap);
-    units3 = dev_buf<uint4>(res, 2 * pl.max_units); overflow3 = dev_buf<uint4>(res, (size_t)2 * pl.overflow_cap);
+    // (the narrow filters' units twice: list order and hand-out order - pq3_run::units_ord)
+    units3 = dev_buf<uint4>(res, (res.tune.pq_unit_order != 0 && !w ? 4 : 2) * pl.max_units); overflow3 = dev_buf<uint4>(res, (size_t)2 * pl.overflow_cap);
     fb_items = dev_buf<work_item>(res, mc ? np : 0);
     bq3 = dev_buf<uint4>(res, f4w ? (np + (w ? (size_t)32 * (nl + 1) : 0)) * (idx.rot_dim / 8) : 0);
     thr3 = dev_buf<float>(res, f4w ? np : 0);
@@ -2312,8 +2313,17 @@ void report_head_stats(resources& res, const unsigned long long* d_stats, int wg
 
 void report_filter_stats(resources& res, const unsigned long long* d_stats, const uint32_t* counters)  // bit 1024
 {
-  auto hs = to_host(res, d_stats, 8);
+  auto hs = to_host(res, d_stats, kPq3Stats);
   g_pq3_last_stats[0] = hs[0]; g_pq3_last_stats[1] = hs[1]; g_pq3_last_stats[2] = hs[2]; g_pq3_last_stats[3] = hs[7];
+  if (hs[19] != 0) {  // pq_filter4_kernel's STATS build: cost of a subtile by query groups, and how the kernel ends
+    fprintf(stderr, "[pq_scan3] wave cycles per subtile at 1 / 2 / 3 / 4 query groups: %.0f / %.0f / %.0f / %.0f (subtiles %llu / %llu / %llu / %llu)\n",
+            (double)hs[8] / std::max<unsigned long long>(1, hs[12]), (double)hs[9] / std::max<unsigned long long>(1, hs[13]),
+            (double)hs[10] / std::max<unsigned long long>(1, hs[14]), (double)hs[11] / std::max<unsigned long long>(1, hs[15]),
+            hs[12], hs[13], hs[14], hs[15]);
+    const double span = (double)(hs[17] - hs[16]);
+    fprintf(stderr, "[pq_scan3] waves %llu, first ticket to last unit's end %.0f ticks of the real-time counter, tail idle share %.4f\n", hs[19],
+            span, 1.0 - (double)hs[18] / std::max(1.0, (double)hs[19] * span));
+  }
   fprintf(stderr, "[pq_scan3] units %llu; wave cycles per unit: prologue %.0f, loop %.0f (slow path %.0f); per subtile %.0f\n", hs[7],
           (double)hs[4] / std::max<unsigned long long>(1, hs[7]), (double)hs[5] / std::max<unsigned long long>(1, hs[7]),
           (double)hs[6] / std::max<unsigned long long>(1, hs[7]), (double)hs[5] / std::max<unsigned long long>(1, hs[2]));
@@ -2430,8 +2440,15 @@ void run_filter_tail(const pq_search_ctx& c, scan_args a, int64_t nq)
   r.unit_rows = pl.unit_rows; r.xcd_ticket = s.tickets.data() + 2 * 8 * 32; r.fb_items = s.fb_items.data();
   r.filter_bits = c.filter_bits; r.overflow = s.overflow3.data(); r.overflow_cap = pl.overflow_cap;
   r.bq = (pl.filter4 || wide) ? s.bq3.data() : nullptr; r.thr = s.thr3.data();
-  dev_buf<unsigned long long> st3(res, (a.dbg & 1024) ? 8 : 0);
-  if (a.dbg & 1024) HIP_TRY(hipMemsetAsync(st3.data(), 0, st3.bytes(), res.stream));
+  if (res.tune.pq_unit_order != 0 && !wide) {
+    r.unit_order = res.tune.pq_unit_order;
+    r.units_ord  = s.units3.data() + 2 * pl.max_units;
+  }
+  dev_buf<unsigned long long> st3(res, (a.dbg & 1024) ? kPq3Stats : 0);
+  if (a.dbg & 1024) {
+    HIP_TRY(hipMemsetAsync(st3.data(), 0, st3.bytes(), res.stream));
+    HIP_TRY(hipMemsetAsync(st3.data() + 16, 0xff, sizeof(unsigned long long), res.stream));  // (a minimum)
+  }
   r.stats = st3.data(); r.filter_dbg = (a.dbg >> 16) & 255;  // CUVS_AMD_SCAN_DEBUG bits 16..23
   if (pl.overlap) {
     // the helper stream: work units, B operands and norms of the tail pairs (nothing here reads the head phase's bounds);
@@ -2458,6 +2475,11 @@ void run_filter_tail(const pq_search_ctx& c, scan_args a, int64_t nq)
   if (pl.head1) launch_head_scan(c, a); else launch_lut_scan(res, pl, a);
   pq3_merge(res, r, s.top_d.data(), s.top_i.data());
   if (a.dbg & 1024) report_filter_stats(res, st3.data(), r.counters);
+  if ((a.dbg & 1024) && (a.dbg & (1 << 24))) {  // + bit 24: rows and tail pairs of every list (scripts/unit_order_model.py reads them)
+    const auto off = to_host(res, r.pair_off + c.idx.n_lists, (size_t)c.idx.n_lists + 1);
+    fprintf(stderr, "[pq_units] unit_rows %u\n", pl.unit_rows);
+    for (uint32_t L = 0; L < c.idx.n_lists; ++L) fprintf(stderr, "[pq_units] %u %u\n", c.idx.h_list_sizes[L], off[L + 1] - off[L]);
+  }
 }
 
 // ------------------------------------------------------------------ one batch of queries

@@ -169,6 +169,11 @@ CUVS_EXPORT void cuvsAmdIvfPqLastFilterStats(unsigned long long out[4]);
 /* the same + out[4] = (query, probe) pairs handed back to the LUT scan kernels, out[5] = candidates that went through the
  * shared overflow list */
 CUVS_EXPORT void cuvsAmdIvfPqLastFilterStats6(unsigned long long out[6]);
+/* Test hook over the functions that hand the matrix-core filter's work units to its waves: out = {cost key of a unit of `rows`
+ * rows and `groups` groups of 32 queries when row chunks have up to `unit_rows` rows (0: no rows, placed last), units in the
+ * share of XCD `xcd` out of `n_units`, array position of that share's ticket `t`} - strided != 0: the shares of the cost order. */
+CUVS_EXPORT void cuvsAmdIvfPqUnitOrderHook(uint32_t rows, uint32_t groups, uint32_t unit_rows, uint32_t n_units, uint32_t xcd,
+                                           uint32_t t, int strided, uint32_t out[3]);
 
 /* Sweeps of the Jacobi eigensolver that the calling thread's last cuvsPcaFit / cuvsPcaFitTransform ran (a sweep that rotated
  * nothing is not counted). Test and tuning hook for cuvsPcaParams::tol and n_iterations. */
