@@ -373,3 +373,74 @@ extern "C" __attribute__((visibility("default"))) int cuvsAmdKMeansBalancedFit(u
     if (labels) kmeans_predict<float>(*as_res(res), x, n, dim, centers, n_clusters, labels);
   });
 }
+
+// The same with the metric switch; labels are predicted against the returned centres (inner product: largest dot product).
+extern "C" __attribute__((visibility("default"))) int cuvsAmdKMeansBalancedFitEx(uintptr_t res, const float* x, int64_t n,
+                                                                                  int64_t dim, int n_clusters, int n_iters,
+                                                                                  int hierarchical, int inner_product,
+                                                                                  float* centers, uint32_t* labels)
+{
+  using namespace cuvs_amd;
+  return translate_exceptions([=] {
+    kmeans_params p;
+    p.n_iters       = n_iters;
+    p.hierarchical  = hierarchical != 0;
+    p.inner_product = inner_product != 0;
+    kmeans_balanced_fit(*as_res(res), x, n, dim, n_clusters, p, centers);
+    if (labels) predict_f32(*as_res(res), x, n, dim, (int)dim, centers, n_clusters, labels, p.inner_product);
+  });
+}
+
+// The steps of the trainer on the caller's device buffers; x has row pitch ld (in elements) everywhere.
+extern "C" __attribute__((visibility("default"))) int cuvsAmdKMeansBuildClusters(uintptr_t res, const float* x, int64_t n,
+                                                                                  int64_t ld, int dim, int k, int n_iters,
+                                                                                  int inner_product, float* centers,
+                                                                                  uint32_t* labels, uint32_t* sizes)
+{
+  using namespace cuvs_amd;
+  return translate_exceptions([=] {
+    CUVS_EXPECTS(n > 0 && k > 0 && dim > 0 && ld >= dim, "cuvsAmdKMeansBuildClusters: bad shape");
+    kmeans_build_clusters(*as_res(res), x, n, ld, dim, k, n_iters, centers, labels, sizes, inner_product != 0);
+  });
+}
+
+extern "C" __attribute__((visibility("default"))) int cuvsAmdKMeansClusterMeans(uintptr_t res, const float* x, int64_t n,
+                                                                                 int64_t ld, int dim, int k,
+                                                                                 const uint32_t* labels, float* centers,
+                                                                                 uint32_t* sizes)
+{
+  using namespace cuvs_amd;
+  return translate_exceptions([=] {
+    CUVS_EXPECTS(n > 0 && k > 0 && dim > 0 && ld >= dim, "cuvsAmdKMeansClusterMeans: bad shape");
+    calc_centers_and_sizes(*as_res(res), x, n, ld, dim, k, labels, centers, sizes);
+  });
+}
+
+// One adjust_centers pass; i_primes (host, in/out) is the position in the prime table, adjusted (host) the returned flag.
+extern "C" __attribute__((visibility("default"))) int cuvsAmdKMeansAdjustCenters(uintptr_t res, float* centers, int k, int dim,
+                                                                                  const float* x, int64_t ld, int64_t n,
+                                                                                  const uint32_t* labels, const uint32_t* sizes,
+                                                                                  float threshold, int* i_primes, int* adjusted)
+{
+  using namespace cuvs_amd;
+  return translate_exceptions([=] {
+    CUVS_EXPECTS(n > 0 && k > 0 && dim > 0 && ld >= dim && i_primes != nullptr && adjusted != nullptr,
+                 "cuvsAmdKMeansAdjustCenters: bad arguments");
+    auto& r = *as_res(res);
+    dev_buf<int> flag(r, 1);
+    int ip    = *i_primes;
+    *adjusted = adjust_centers(r, centers, k, dim, x, ld, n, labels, sizes, threshold, flag.data(), ip) ? 1 : 0;
+    *i_primes = ip;
+  });
+}
+
+extern "C" __attribute__((visibility("default"))) int cuvsAmdGroupByLabel(uintptr_t res, const uint32_t* labels, int64_t n,
+                                                                           uint32_t n_clusters, uint32_t* perm,
+                                                                           uint32_t* offsets)
+{
+  using namespace cuvs_amd;
+  return translate_exceptions([=] {
+    CUVS_EXPECTS(n > 0 && n_clusters > 0, "cuvsAmdGroupByLabel: bad shape");
+    group_by_label(*as_res(res), labels, n, n_clusters, perm, offsets);
+  });
+}

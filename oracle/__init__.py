@@ -259,15 +259,80 @@ def cagra_mst(knn_graph, graph_degree):
     return mst, cnt, int(left)
 
 
-def kmeans_balanced_fit(x, n_clusters, n_iters=20, hierarchical=True):
-    """CPU twin of the balanced k-means (cuvs_amd/csrc/kmeans_balanced.hip). Returns (centers, labels)."""
+KMEANS_TRACE = ("adjust_passes", "extra_iters", "primes_skipped", "meso_truncated", "meso_cyclic", "meso_empty",
+                "empty_at_return", "flat_route")
+
+
+def _trace_arg(trace):
+    """trace: None, or a C-contiguous int64 array of 8 counters (KMEANS_TRACE names them) that the call overwrites."""
+    if trace is None:
+        return None
+    assert trace.dtype == np.int64 and trace.shape == (8,) and trace.flags.c_contiguous
+    return _p(trace)
+
+
+def _pitched(buf, col0, dim):
+    """Rows of a C-contiguous float32 matrix `buf`, columns [col0, col0 + dim): (buf kept alive, pointer, n, ld, dim)."""
+    buf = _f32(buf)
+    n, ld = buf.shape
+    dim = ld - col0 if dim is None else int(dim)
+    assert 0 <= col0 and dim >= 1 and col0 + dim <= ld
+    return buf, C.c_void_p(buf.ctypes.data + 4 * col0), n, ld, dim
+
+
+def kmeans_balanced_fit(x, n_clusters, n_iters=20, hierarchical=True, inner_product=False, trace=None):
+    """CPU twin of the balanced k-means (cuvs_amd/csrc/kmeans_balanced.hip). Returns (centers, labels); the labels are
+    predicted against the returned centres (inner_product: the largest dot product)."""
     x = _f32(x)
     n, dim = x.shape
     centers = np.empty((n_clusters, dim), np.float32)
     labels = np.empty(n, np.uint32)
-    lib().oracle_kmeans_balanced_fit(_p(x), C.c_int64(n), C.c_int(dim), C.c_int(n_clusters), C.c_int(n_iters),
-                                     C.c_int(int(hierarchical)), _p(centers), _p(labels))
+    lib().oracle_kmeans_balanced_fit_ex(_p(x), C.c_int64(n), C.c_int(dim), C.c_int(n_clusters), C.c_int(n_iters),
+                                        C.c_int(int(hierarchical)), C.c_int(int(inner_product)), _p(centers), _p(labels),
+                                        _trace_arg(trace))
     return centers, labels
+
+
+def kmeans_build_clusters(buf, n_clusters, n_iters=10, inner_product=False, col0=0, dim=None, trace=None):
+    """Twin of kmeans_build_clusters on columns [col0, col0 + dim) of `buf` (row pitch buf.shape[1]).
+    Returns (centers, labels, sizes)."""
+    buf, px, n, ld, dim = _pitched(buf, col0, dim)
+    centers = np.empty((n_clusters, dim), np.float32)
+    labels = np.empty(n, np.uint32)
+    sizes = np.empty(n_clusters, np.uint32)
+    lib().oracle_kmeans_build_clusters_ex(px, C.c_int64(n), C.c_int64(ld), C.c_int(dim), C.c_int(n_clusters),
+                                          C.c_int(n_iters), C.c_int(int(inner_product)), _p(centers), _p(labels), _p(sizes),
+                                          _trace_arg(trace))
+    return centers, labels, sizes
+
+
+def kmeans_cluster_means(buf, labels, n_clusters, col0=0, dim=None):
+    """Twin of calc_centers_and_sizes (the M-step) for given labels. Returns (centers, sizes)."""
+    buf, px, n, ld, dim = _pitched(buf, col0, dim)
+    labels = np.ascontiguousarray(labels, dtype=np.uint32)
+    assert labels.shape == (n,) and (labels < n_clusters).all()
+    centers = np.empty((n_clusters, dim), np.float32)
+    sizes = np.empty(n_clusters, np.uint32)
+    lib().oracle_kmeans_calc_centers(px, C.c_int64(n), C.c_int64(ld), C.c_int(dim), C.c_int(n_clusters), _p(labels),
+                                     _p(centers), _p(sizes))
+    return centers, sizes
+
+
+def kmeans_adjust_centers(centers, buf, labels, sizes, threshold, i_primes, col0=0, dim=None):
+    """Twin of one adjust_centers pass. Returns (new centers, adjusted flag, new i_primes)."""
+    buf, px, n, ld, dim = _pitched(buf, col0, dim)
+    centers = _f32(centers).copy()
+    k = centers.shape[0]
+    assert centers.shape == (k, dim)
+    labels = np.ascontiguousarray(labels, dtype=np.uint32)
+    sizes = np.ascontiguousarray(sizes, dtype=np.uint32)
+    assert labels.shape == (n,) and sizes.shape == (k,) and (labels < k).all()
+    ip = C.c_int(int(i_primes))
+    fn = lib().oracle_kmeans_adjust_centers
+    fn.restype = C.c_int
+    adjusted = fn(_p(centers), C.c_int(k), C.c_int(dim), px, C.c_int64(ld), C.c_int64(n), _p(labels), _p(sizes),
+                  C.c_float(threshold), C.byref(ip))
+    return centers, int(adjusted), ip.value
 
 
 def kmeans_lloyd(x, init_centroids, max_iter=300, tol=1e-4, sample_weights=None):
