@@ -1,2 +1,2 @@
 """Clustering (reference: python/cuvs/cuvs/cluster/)."""
-from . import agglomerative, kmeans  # noqa: F401
+from . import agglomerative, kmeans, spectral  # noqa: F401

@@ -246,15 +246,6 @@ const float* normalized_weights(resources& res, const float* w, int64_t n, dev_b
   return storage.data();
 }
 
-struct lloyd_params {
-  int n_clusters;
-  int init;  // cuvsKMeansInitMethod
-  int max_iter;
-  double tol;
-  int n_init;
-  uint64_t seed = 0;  // the reference's default rng_state seed
-};
-
 void seed_centroids(resources& res, const float* x, int64_t n, int dim, const float* w, const lloyd_params& p,
                     uint64_t seed, float* centers)
 {
@@ -294,7 +285,9 @@ void seed_centroids(resources& res, const float* x, int64_t n, int dim, const fl
   sync(res);
 }
 
-// x, centroids on device; w = normalized weights or nullptr
+}  // namespace
+
+// x, centroids on device; w = normalized weights or nullptr (declared in ops.hpp: spectral.hip fits the embedding with it)
 void lloyd_fit(resources& res, const float* x, int64_t n, int dim, const float* w, const lloyd_params& p,
                float* centroids, double* inertia, int* n_iter)
 {
@@ -348,6 +341,8 @@ void lloyd_fit(resources& res, const float* x, int64_t n, int dim, const float* 
     }
   }
 }
+
+namespace {
 
 bool metric_ok(int m) { return metric_is_l2(m); }
 

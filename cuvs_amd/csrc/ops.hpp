@@ -116,6 +116,20 @@ template <typename T>
 void kmeans_predict(resources& res, const T* x, int64_t n, int64_t dim, const float* centers,
                     int n_clusters, uint32_t* labels);
 
+// ---------------------------------------------------------------- kmeans_capi.hip
+struct lloyd_params {
+  int n_clusters;
+  int init;  // cuvsKMeansInitMethod
+  int max_iter;
+  double tol;
+  int n_init;
+  uint64_t seed = 0;  // the reference's default rng_state seed
+};
+// The non-hierarchical Lloyd fit behind cuvsKMeansFit: x [n, dim] and centroids [n_clusters, dim] on the device, w the
+// normalised sample weights or nullptr; inertia and n_iter (host, optional) are those of the best of the n_init trials.
+void lloyd_fit(resources& res, const float* x, int64_t n, int dim, const float* w, const lloyd_params& p, float* centroids,
+               double* inertia, int* n_iter);
+
 // ---------------------------------------------------------------- ivf_pq_build.hip
 // make_rotation_matrix(rot_dim, dim, force_random = true): the top-left [rot_dim, dim] block of a seeded random orthogonal matrix
 std::vector<float> random_rotation_matrix(uint32_t rot_dim, uint32_t dim);
