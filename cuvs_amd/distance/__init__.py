@@ -61,3 +61,6 @@ def pairwise_distance(X, Y, out=None, metric="euclidean", p=2.0, resources=None)
     if sync:
         resources.sync()
     return out
+
+
+from ._sparse import SPARSE_DISTANCES, set_sparse_walk_form, sparse_last_stats, sparse_pairwise_distance, validate_csr  # noqa: E402,F401

@@ -11,6 +11,7 @@
 #include <cuvs_amd/eps_neighbors.h>
 #include <cuvs_amd/extensions.h>
 #include <cuvs_amd/ivf_rabitq.h>
+#include <cuvs_amd/sparse.h>
 
 #include <array>
 #include <cstdint>
@@ -119,6 +120,35 @@ struct c_params {
 };
 }  // namespace detail
 
+// a canonical CSR matrix the caller owns, on the device (include/cuvs_amd/sparse.h): indptr [rows + 1], indices and data [nnz]
+struct csr_view {
+  const int32_t* indptr  = nullptr;
+  const int32_t* indices = nullptr;
+  const float* data      = nullptr;
+  int64_t rows = 0, cols = 0, nnz = 0;
+};
+
+namespace detail {
+struct csr_tensors {
+  vector_tensor<const int32_t> indptr, indices;
+  vector_tensor<const float> data;
+  explicit csr_tensors(const csr_view& v) : indptr(v.indptr, v.rows + 1), indices(v.indices, v.nnz), data(v.data, v.nnz) {}
+};
+}  // namespace detail
+
+namespace distance {
+// distance.hpp:389-466: pairwise_distance(res, csr x, csr y, dense out, metric, metric_arg); out is [x.rows, y.rows]
+inline void pairwise_distance(const resources& res, const csr_view& x, const csr_view& y, device_matrix_view<float> out,
+                              cuvsDistanceType metric, float metric_arg = 2.0f)
+{
+  detail::csr_tensors tx(x), ty(y);
+  detail::tensor<float> o(out);
+  check(cuvsAmdSparsePairwiseDistance(res.get(), &tx.indptr.m, &tx.indices.m, &tx.data.m, x.rows, &ty.indptr.m, &ty.indices.m, &ty.data.m,
+                                      y.rows, x.cols, o.get(), metric, metric_arg),
+        "cuvsAmdSparsePairwiseDistance");
+}
+}  // namespace distance
+
 namespace neighbors {
 
 namespace filtering {
@@ -162,6 +192,44 @@ void search(const resources& res, const index<T>& idx, device_matrix_view<const 
   detail::tensor<float> d(distances);
   cuvsFilter none{0, NO_FILTER};
   check(cuvsBruteForceSearch(res.get(), idx.get(), q.get(), n.get(), d.get(), none), "cuvsBruteForceSearch");
+}
+
+// brute_force.hpp:594-700: sparse_index, build, sparse_search_params, search - the index VIEWS the three arrays (keep them alive)
+class sparse_index {
+ public:
+  sparse_index() { check(cuvsAmdSparseBruteForceIndexCreate(&h_), "cuvsAmdSparseBruteForceIndexCreate"); }
+  ~sparse_index() { if (h_) cuvsAmdSparseBruteForceIndexDestroy(h_); }
+  sparse_index(sparse_index&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  sparse_index(const sparse_index&) = delete;
+  cuvsAmdSparseBruteForceIndex_t get() const { return h_; }
+
+ private:
+  cuvsAmdSparseBruteForceIndex_t h_ = nullptr;
+};
+struct sparse_search_params {
+  int batch_size_index = 2 << 14;
+  int batch_size_query = 2 << 14;
+};
+inline sparse_index build(const resources& res, const csr_view& dataset, cuvsDistanceType metric = L2Expanded, float metric_arg = 2.0f)
+{
+  sparse_index idx;
+  detail::csr_tensors t(dataset);
+  check(cuvsAmdSparseBruteForceBuild(res.get(), &t.indptr.m, &t.indices.m, &t.data.m, dataset.rows, dataset.cols, metric, metric_arg,
+                                     idx.get()),
+        "cuvsAmdSparseBruteForceBuild");
+  return idx;
+}
+// IdxT: int64_t or int32_t (the reference's type)
+template <typename IdxT>
+void search(const resources& res, const sparse_search_params& params, const sparse_index& idx, const csr_view& queries,
+            device_matrix_view<IdxT> neighbors, device_matrix_view<float> distances)
+{
+  detail::csr_tensors q(queries);
+  detail::tensor<IdxT> n(neighbors);
+  detail::tensor<float> d(distances);
+  check(cuvsAmdSparseBruteForceSearch(res.get(), idx.get(), &q.indptr.m, &q.indices.m, &q.data.m, queries.rows, neighbors.cols,
+                                      params.batch_size_index, params.batch_size_query, n.get(), d.get()),
+        "cuvsAmdSparseBruteForceSearch");
 }
 }  // namespace brute_force
 
