@@ -113,6 +113,7 @@ struct tuning {
   int hnsw_pack_rows    = 0;      // CUVS_AMD_HNSW_PACK_ROWS: rows per chunk of the level-0 record packing of cuvsHnswFromCagra (test hook: several chunks on a small index)
   int hnsw_pack_host    = 0;      // CUVS_AMD_HNSW_PACK_HOST=1: the records are interleaved by the host loop instead of hnsw_pack_kernel (comparator of the timing and of the tests)
   int eps_slab_rows     = 0;      // CUVS_AMD_EPS_SLAB_ROWS: rows of x per slab of the epsilon-neighbourhood search (test hook: several slabs at a small m)
+  int stats_slab_rows   = 0;      // CUVS_AMD_STATS_SLAB_ROWS: rows per slab of the silhouette score and of the neighbour ranks (test hook: several slabs at a small n)
 };
 tuning load_tuning_from_env();
 

@@ -226,6 +226,7 @@ tuning load_tuning_from_env()
   t.hnsw_pack_rows   = geti("CUVS_AMD_HNSW_PACK_ROWS", 0);
   t.hnsw_pack_host   = geti("CUVS_AMD_HNSW_PACK_HOST", 0);
   t.eps_slab_rows    = geti("CUVS_AMD_EPS_SLAB_ROWS", 0);
+  t.stats_slab_rows  = geti("CUVS_AMD_STATS_SLAB_ROWS", 0);
   return t;
 }
 
