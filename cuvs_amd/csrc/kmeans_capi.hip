@@ -361,7 +361,11 @@ const float* weight_ptr(DLManagedTensor* sw, int64_t n, bool need_device, resour
   CUVS_EXPECTS(dtype_is(t.dtype, kDLFloat, 32), "sample_weight must be float32");
   CUVS_EXPECTS(t.ndim == 1 && t.shape[0] == n, "sample_weight must have n_samples entries");
   if (is_device_accessible(t)) return static_cast<const float*>(dl_data(t));
-  CUVS_EXPECTS(!need_device && is_host_accessible(t), "sample_weight must be host accessible when X is on host");
+  // X on the device: the reference converts the weights to a device view and fails in from_dlpack (interop.hpp:121)
+  CUVS_EXPECTS(!need_device,
+               "sample_weight: device_type mismatch between return mdspan and DLTensor (X is on device memory, "
+               "sample_weight is not)");
+  CUVS_EXPECTS(is_host_accessible(t), "sample_weight must be host accessible when X is on host");
   staged = dev_buf<float>(res, n);
   copy_async(res, staged.data(), dl_data(t), n * sizeof(float));
   return staged.data();

@@ -335,13 +335,15 @@ def kmeans_adjust_centers(centers, buf, labels, sizes, threshold, i_primes, col0
     return centers, int(adjusted), ip.value
 
 
-def kmeans_lloyd(x, init_centroids, max_iter=300, tol=1e-4, sample_weights=None):
+def kmeans_lloyd(x, init_centroids, max_iter=300, tol=1e-4, sample_weights=None, trace=False):
     """Lloyd iterations as the reference runs them (cpp/src/cluster/detail/kmeans.cuh:813-925): per iteration the
     cost against the CURRENT centroids, weighted means (a cluster with zero weight keeps its centroid,
     kmeans_common.cuh:585-600), squared centroid shift, then the stopping rule of kmeans_common.cuh:629-648 evaluated in
     float32 like the reference's DataT. Weights are rescaled to sum to n (kmeans.cuh:713-726). Arithmetic is float64
     here: the HIP path is compared within a stated tolerance, not bit for bit.
-    Returns (centroids float32 [k, d], labels int32 [n], inertia, n_iter)."""
+    Returns (centroids float32 [k, d], labels int32 [n], inertia, n_iter); with trace=True a fifth item, one dict per
+    iteration: cost (float64), ratio (float32 cost / prior cost, None in the first iteration), shift (float64) and
+    which branches of the stopping rule fired (by_ratio, by_shift)."""
     x64 = np.asarray(x, dtype=np.float64)
     cur = np.asarray(init_centroids, dtype=np.float64).copy()
     n, k = x64.shape[0], cur.shape[0]
@@ -352,7 +354,7 @@ def kmeans_lloyd(x, init_centroids, max_iter=300, tol=1e-4, sample_weights=None)
         lab = d.argmin(1)
         return lab, ((x64 - c[lab]) ** 2).sum(1)
 
-    prior, ran = 0.0, 0
+    prior, ran, steps = 0.0, 0, []
     for it in range(1, max_iter + 1):
         lab, dist = assign(cur)
         cost = float((w * dist).sum())
@@ -364,10 +366,159 @@ def kmeans_lloyd(x, init_centroids, max_iter=300, tol=1e-4, sample_weights=None)
                 nxt[c] = (w[m, None] * x64[m]).sum(0) / ws
         shift = float(((nxt - cur) ** 2).sum())
         cur, ran = nxt, it
-        done = cost != 0.0 and it > 1 and np.float32(cost / prior) > np.float32(1.0) - np.float32(tol)
-        done = done or np.float32(shift) < np.float32(tol)
+        by_ratio = bool(cost != 0.0 and it > 1 and np.float32(cost / prior) > np.float32(1.0) - np.float32(tol))
+        by_shift = bool(np.float32(shift) < np.float32(tol))
+        done = by_ratio or by_shift
+        steps.append({"cost": cost, "ratio": float(np.float32(cost / prior)) if it > 1 and prior != 0.0 else None,
+                      "ratio64": cost / prior if it > 1 and prior != 0.0 else None, "shift": shift,
+                      "by_ratio": by_ratio, "by_shift": by_shift})
         prior = cost
         if done:
             break
     lab, dist = assign(cur)
-    return cur.astype(np.float32), lab.astype(np.int32), float((w * dist).sum()), ran
+    out = (cur.astype(np.float32), lab.astype(np.int32), float((w * dist).sum()), ran)
+    return out + (steps,) if trace else out
+
+
+def kmeans_lloyd_margin(steps, tol, dim):
+    """True when no decision of the stopping rule in a kmeans_lloyd trace can be flipped by float32 rounding on the
+    device. An iteration is safe when its shift is at most tol / 2 (it stops whatever the ratio says), or when its shift
+    is at least 2 * tol and its cost ratio is clear of the threshold 1 - tol:
+      * by 1e-3 where the float32 threshold is below 1 (the two costs agree with float64 far better than that);
+      * where tol is below the float32 epsilon the threshold is exactly 1.0f, which only a cost that RISES by 2^-24 can
+        exceed. Each row's distance carries at most (dim + 1) roundings of 2^-24, so the device's ratio is within
+        2 * (dim + 2) * 2^-24 of the float64 one: the float64 ratio must stay that far below 1."""
+    thr = np.float32(1.0) - np.float32(tol)
+    for s in steps:
+        if s["shift"] <= 0.5 * tol:
+            continue
+        if s["shift"] < 2.0 * tol:
+            return False
+        if s["ratio"] is None:
+            continue
+        if thr == np.float32(1.0):
+            if s["ratio64"] > 1.0 - 2.0 * (dim + 2) * 2.0 ** -24:
+                return False
+        elif abs(s["ratio"] - float(thr)) < 1e-3:
+            return False
+    return True
+
+
+# ---- seeding of the Lloyd fit (cuvs_amd/csrc/kmeans_capi.hip: seed_centroids), restated step for step ----------------
+
+_M64 = (1 << 64) - 1
+
+
+class mt19937_64:
+    """std::mt19937_64: seeded with 5489 its 10000th output is 9981545732273789042 ([rand.predef])."""
+
+    def __init__(self, seed):
+        s = [int(seed) & _M64]
+        for i in range(1, 312):
+            s.append((6364136223846793005 * (s[-1] ^ (s[-1] >> 62)) + i) & _M64)
+        self.s, self.i = s, 312
+
+    def _twist(self):
+        s = self.s
+        for i in range(312):
+            y = (s[i] & 0xFFFFFFFF80000000) | (s[(i + 1) % 312] & 0x7FFFFFFF)
+            s[i] = s[(i + 156) % 312] ^ (y >> 1) ^ (0xB5026F5AA96619E9 if y & 1 else 0)
+        self.i = 0
+
+    def __call__(self):
+        if self.i >= 312:
+            self._twist()
+        y = self.s[self.i]
+        self.i += 1
+        y ^= (y >> 29) & 0x5555555555555555
+        y ^= (y << 17) & 0x71D67FFFEDA60000
+        y ^= (y << 37) & 0xFFF7EEE000000000
+        return y ^ (y >> 43)
+
+
+def kmeans_trial_seeds(n_init, seed=0):
+    """The seed each of the n_init trials of a fit hands to its seeding: successive outputs of mt19937_64(seed)."""
+    gen = mt19937_64(seed)
+    return [gen() for _ in range(n_init)]
+
+
+def _mix64(z):
+    """splitmix64 finaliser on uint64 arrays (wraps around like the device code)."""
+    z = z + np.uint64(0x9E3779B97F4A7C15)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def _row_sqdist_f32(x, c):
+    """|x_i - c|^2 as one 64-lane wave computes it: lane l accumulates dims l, l + 64, ... by fma, then a butterfly sum."""
+    n, dim = x.shape
+    t = np.zeros((n, -(-dim // 64) * 64), dtype=np.float32)
+    t[:, :dim] = x - c[None, :]
+    t = t.reshape(n, -1, 64)
+    acc = np.zeros((n, 64), dtype=np.float32)
+    for j in range(t.shape[1]):  # fma: exact product (48 bits fit a double), one rounding of the sum
+        acc = (t[:, j].astype(np.float64) ** 2 + acc.astype(np.float64)).astype(np.float32)
+    lanes = np.arange(64)
+    for off in (32, 16, 8, 4, 2, 1):
+        acc = acc + acc[:, lanes ^ off]
+    return acc[:, 0]
+
+
+def kmeans_seed_rows(x, k, init, trial_seed, sample_weights=None, forced=None):
+    """The k rows seed_centroids picks for one trial, and a per-round trace.
+
+    init is "Random" (Floyd's algorithm on the generator, ids sorted; integer only, so exact) or "KMeansPlusPlus" (the
+    exponential race of pp_round_kernel / pp_pick_kernel: per round j, mind = min(mind, |x - c_j|^2) in float32, a
+    counter hash of (round seed, j, row) mapped to u in float32 exactly as the kernel maps it (its top value rounds to
+    1.0, whose key is -inf and never wins), key = w * mind / -log(u), arg max with ties to the smaller row). Weights
+    are rescaled to sum to n in float32 like normalized_weights; the first seed ignores them. `forced`, a list of row
+    ids, replaces the twin's own pick in the rounds it covers (entry 0 is the first seed), so a comparison can follow
+    another implementation's picks. The trace holds one dict per k-means++ round: pick (the twin's own arg max),
+    best, second (keys), second_row, and used (the row carried forward). The device takes the logarithm with its
+    fast instruction; the twin takes it in float64 and rounds to float32."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    n, dim = x.shape
+    gen = mt19937_64(trial_seed)
+    if init == "Random":
+        chosen, ids = set(), []
+        for j in range(n - k, n):
+            t = gen() % (j + 1)
+            if t in chosen:
+                t = j
+            chosen.add(t)
+            ids.append(t)
+        return sorted(ids), []
+    assert init == "KMeansPlusPlus"
+    w = None
+    if sample_weights is not None:
+        w32 = np.asarray(sample_weights, dtype=np.float32)
+        w = w32 * np.float32(n / float(w32.astype(np.float64).sum()))
+    forced = list(forced) if forced is not None else []
+    first = gen() % n
+    round_seed = np.uint64(gen())
+    ids = [int(forced[0]) if forced else int(first)]
+    rows = np.arange(n, dtype=np.uint64)
+    mind, steps = None, []
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        for j in range(k - 1):
+            d = _row_sqdist_f32(x, x[ids[j]])
+            mind = d if mind is None else np.minimum(d, mind)
+            h = _mix64(round_seed ^ _mix64((np.uint64(j + 1) << np.uint64(40)) ^ rows))
+            u = ((h >> np.uint64(40)).astype(np.float32) + np.float32(0.5)) * np.float32(1.0 / 16777216.0)
+            e = (-np.log(u.astype(np.float64))).astype(np.float32)
+            key = (mind if w is None else w * mind) / e
+            live = np.where(key > np.float32(-1.0), key, np.float32(-np.inf))  # NaN and -inf never beat the start, -1
+            pick = int(np.argmax(live))  # first occurrence: ties keep the smaller row
+            if not live[pick] > -1.0:
+                pick, best, second, second_row = 0, float("-inf"), float("-inf"), -1  # pp_pick_kernel's fallback
+            else:
+                best = float(live[pick])
+                rest = live.copy()
+                rest[pick] = -np.inf
+                second_row = int(np.argmax(rest))
+                second = float(rest[second_row])
+            used = int(forced[j + 1]) if j + 1 < len(forced) else pick
+            steps.append({"pick": pick, "best": best, "second": second, "second_row": second_row, "used": used})
+            ids.append(used)
+    return ids, steps
