@@ -92,6 +92,7 @@ _NP_DT = {
     np.dtype("float64"): (kDLFloat, 64),
     np.dtype("int8"): (kDLInt, 8),
     np.dtype("uint8"): (kDLUInt, 8),
+    np.dtype("int16"): (kDLInt, 16),
     np.dtype("int32"): (kDLInt, 32),
     np.dtype("uint32"): (kDLUInt, 32),
     np.dtype("int64"): (kDLInt, 64),

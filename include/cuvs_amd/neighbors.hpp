@@ -11,9 +11,11 @@
 #include <cuvs_amd/eps_neighbors.h>
 #include <cuvs_amd/extensions.h>
 #include <cuvs_amd/ivf_rabitq.h>
+#include <cuvs_amd/scann.h>
 #include <cuvs_amd/sparse.h>
 
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <memory>
 #include <stdexcept>
@@ -72,6 +74,7 @@ DLDataType dl_dtype()
   else if constexpr (std::is_same_v<U, uint32_t>) return {kDLUInt, 32, 1};
   else if constexpr (std::is_same_v<U, int32_t>) return {kDLInt, 32, 1};
   else if constexpr (std::is_same_v<U, bool>) return {kDLBool, 8, 1};
+  else if constexpr (std::is_same_v<U, int16_t>) return {kDLInt, 16, 1};
   else if constexpr (sizeof(U) == 2) return {kDLFloat, 16, 1};  // __half / _Float16
   else static_assert(sizeof(U) == 0, "unsupported element type");
 }
@@ -722,6 +725,113 @@ inline std::array<uint64_t, 4> last_stats()
   return out;
 }
 }  // namespace ball_cover
+
+namespace experimental {
+namespace scann {
+// scann.hpp: build-only. Partitions by balanced k-means, AVQ centres, SOAR labels, PQ codes of both residuals, optional bf16 rows,
+// and the files open-source ScaNN reads (include/cuvs_amd/scann.h). pq_dim is the width of a subspace.
+struct index_params {
+  cuvsDistanceType metric     = L2Expanded;
+  float metric_arg            = 2.0f;
+  uint32_t n_leaves           = 1000;
+  int64_t kmeans_n_rows_train = 100000;
+  uint32_t kmeans_n_iters     = 24;
+  float partitioning_eta      = 1;
+  float soar_lambda           = 1;
+  uint32_t pq_dim             = 8;
+  uint32_t pq_bits            = 8;
+  int64_t pq_n_rows_train     = 100000;
+  uint32_t pq_train_iters     = 10;
+  bool reordering_bf16        = false;
+  float reordering_noise_shaping_threshold = NAN;
+};
+class index {
+ public:
+  index() { check(cuvsAmdScannIndexCreate(&h_), "cuvsAmdScannIndexCreate"); }
+  ~index() { if (h_) cuvsAmdScannIndexDestroy(h_); }
+  index(index&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  index(const index&) = delete;
+  cuvsAmdScannIndex_t get() const { return h_; }
+  int64_t size() const { return scalar(cuvsAmdScannIndexGetSize); }
+  int64_t dim() const { return scalar(cuvsAmdScannIndexGetDim); }
+  int64_t n_leaves() const { return scalar(cuvsAmdScannIndexGetNLeaves); }
+  int64_t pq_dim() const { return scalar(cuvsAmdScannIndexGetPqDim); }
+  int64_t pq_bits() const { return scalar(cuvsAmdScannIndexGetPqBits); }
+  // views into the index (valid while it lives): the first four on the device, the codes and the bf16 rows on the host
+  device_matrix_view<const float> centers() const { return view<const float>(cuvsAmdScannIndexGetCenters, false); }
+  device_matrix_view<const uint32_t> labels() const { return view<const uint32_t>(cuvsAmdScannIndexGetLabels, false); }
+  device_matrix_view<const uint32_t> soar_labels() const { return view<const uint32_t>(cuvsAmdScannIndexGetSoarLabels, false); }
+  device_matrix_view<const float> pq_codebook() const { return view<const float>(cuvsAmdScannIndexGetPqCodebook, false); }
+  device_matrix_view<const uint8_t> quantized_residuals() const { return view<const uint8_t>(cuvsAmdScannIndexGetCodes, true); }
+  device_matrix_view<const uint8_t> quantized_soar_residuals() const { return view<const uint8_t>(cuvsAmdScannIndexGetSoarCodes, true); }
+  device_matrix_view<const int16_t> bf16_dataset() const
+  {
+    bool has = false;
+    check(cuvsAmdScannIndexHasBf16(h_, &has), "cuvsAmdScannIndexHasBf16");
+    return has ? view<const int16_t>(cuvsAmdScannIndexGetBf16Dataset, true) : device_matrix_view<const int16_t>{nullptr, 0, 0, true};
+  }
+
+ private:
+  int64_t scalar(cuvsError_t (*fn)(cuvsAmdScannIndex_t, int64_t*)) const
+  {
+    int64_t v = 0;
+    check(fn(h_, &v), "cuvsAmdScannIndexGet*");
+    return v;
+  }
+  template <typename T>
+  device_matrix_view<T> view(cuvsError_t (*fn)(cuvsAmdScannIndex_t, DLManagedTensor*), bool on_host) const
+  {
+    DLManagedTensor m{};
+    check(fn(h_, &m), "cuvsAmdScannIndexGet*");
+    device_matrix_view<T> v{static_cast<T*>(m.dl_tensor.data), m.dl_tensor.shape[0], m.dl_tensor.ndim > 1 ? m.dl_tensor.shape[1] : 1, on_host};
+    if (m.deleter) m.deleter(&m);
+    return v;
+  }
+  cuvsAmdScannIndex_t h_ = nullptr;
+};
+using c_index_params = detail::c_params<cuvsAmdScannIndexParams_t, cuvsAmdScannIndexParamsCreate, cuvsAmdScannIndexParamsDestroy>;
+// dataset on the device (make_device_matrix_view) or on the host (make_host_matrix_view: streamed in batches, same index)
+inline index build(const resources& res, const index_params& p, device_matrix_view<const float> dataset)
+{
+  c_index_params cp;
+  *cp.p = cuvsAmdScannIndexParams{p.metric,  p.metric_arg, p.n_leaves,        p.kmeans_n_rows_train, p.kmeans_n_iters, p.partitioning_eta, p.soar_lambda,
+                                  p.pq_dim,  p.pq_bits,    p.pq_n_rows_train, p.pq_train_iters,      p.reordering_bf16,
+                                  p.reordering_noise_shaping_threshold};
+  index idx;
+  detail::tensor<const float> d(dataset);
+  check(cuvsAmdScannBuild(res.get(), cp.p, d.get(), idx.get()), "cuvsAmdScannBuild");
+  return idx;
+}
+// writes the index files into the existing directory
+inline void serialize(const resources& res, const std::string& scann_assets_dir, const index& idx)
+{
+  check(cuvsAmdScannSerialize(res.get(), scann_assets_dir.c_str(), idx.get()), "cuvsAmdScannSerialize");
+}
+// the three stages on their own (device tensors; labels uint32 [n_rows])
+inline void avq_centers(const resources& res, device_matrix_view<const float> dataset, const uint32_t* labels, device_matrix_view<float> centers,
+                        float eta)
+{
+  detail::tensor<const float> d(dataset);
+  detail::tensor<float> c(centers);
+  detail::vector_tensor<const uint32_t> l(labels, dataset.extent(0));
+  check(cuvsAmdScannAvqCenters(res.get(), d.get(), &l.m, c.get(), eta), "cuvsAmdScannAvqCenters");
+}
+inline void soar_labels(const resources& res, device_matrix_view<const float> dataset, device_matrix_view<const float> centers,
+                        const uint32_t* labels, float lambda, uint32_t* soar_labels_out)
+{
+  detail::tensor<const float> d(dataset), c(centers);
+  detail::vector_tensor<const uint32_t> l(labels, dataset.extent(0));
+  detail::vector_tensor<uint32_t> o(soar_labels_out, dataset.extent(0));
+  check(cuvsAmdScannSoarLabels(res.get(), d.get(), c.get(), &l.m, lambda, &o.m), "cuvsAmdScannSoarLabels");
+}
+inline void quantize_bf16(const resources& res, device_matrix_view<const float> dataset, float threshold, device_matrix_view<int16_t> out)
+{
+  detail::tensor<const float> d(dataset);
+  detail::tensor<int16_t> o(out);
+  check(cuvsAmdScannQuantizeBf16(res.get(), d.get(), threshold, o.get()), "cuvsAmdScannQuantizeBf16");
+}
+}  // namespace scann
+}  // namespace experimental
 
 }  // namespace neighbors
 }  // namespace cuvs
