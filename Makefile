@@ -28,6 +28,9 @@ build/ivf_pq_filter4.o: HIPFLAGS += -mllvm -amdgpu-mfma-vgpr-form=1 -fno-honor-n
 # the wide filter: fmaxf chains without canonicalisation (v_max3_f32); its accumulators stay in the accumulation registers
 build/ivf_pq_wide.o: HIPFLAGS += -fno-honor-nans
 
+# the ScaNN scan's fp32 epilogue stays on scalar fp32 instructions (no packed-fp32 forms)
+build/scann_search.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+
 build/%.o: cuvs_amd/csrc/%.hip $(HDRS)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@

@@ -20,6 +20,7 @@
 #include "ops.hpp"
 #include "pq_quantize.hpp"
 #include "scann_host.hpp"
+#include "scann_index.hpp"
 
 #include <cuvs_amd/scann.h>
 
@@ -704,17 +705,7 @@ __global__ void scann_codebook_kernel(const float* __restrict__ book, int64_t bo
   out[t] = book[((int64_t)j * book_n + e) * pq_len + k];
 }
 
-// ================================================================ the index
-struct scann_index {
-  H::params p;
-  int64_t n = 0, dim = 0, n_leaves = 0, n_sub = 0, book_n = 0;
-  dev_buf<float> centers, codebook;
-  dev_buf<uint32_t> labels, soar_labels;
-  std::vector<uint8_t> codes, soar_codes;
-  std::vector<int16_t> bf16;
-  int device = 0;
-};
-
+// ================================================================ the index (scann_index.hpp)
 void check_label_range(resources& res, const uint32_t* labels, int64_t n, int64_t n_leaves)
 {
   dev_buf<uint32_t> word(res, 1);
@@ -882,12 +873,6 @@ uint32_t* labels_of(DLManagedTensor* t, const char* what, int64_t n)
   if (d.ndim != 1 || d.shape[0] != n || !is_c_contiguous(d)) H::refuse("%s must be a contiguous vector of length %lld", what, (long long)n);
   if (!is_device_accessible(d)) H::refuse("%s must be accessible on device memory", what);
   return static_cast<uint32_t*>(dl_data(d));
-}
-
-scann_index& index_of(cuvsAmdScannIndex_t index)
-{
-  if (index == nullptr || index->addr == 0) H::refuse("the ScaNN index is not built");
-  return *reinterpret_cast<scann_index*>(index->addr);
 }
 
 void host_view(DLManagedTensor* out, void* data, DLDataType dt, int64_t rows, int64_t cols)

@@ -1,5 +1,6 @@
 // Host-only parts of the ScaNN index build (scann.hip): the parameter checks, the sizes of the samples and batches, the code
-// unpacking, the label interleaving and the writer of the index files. No HIP and no DLPack types in here:
+// unpacking, the label interleaving, the writer of the index files, and the checks and the list builder of the search
+// (scann_search.hip). No HIP and no DLPack types in here:
 // tests/cpp/scann_host_test.cpp builds this header alone under the sanitizers. The .npy records are byte for byte those of
 // npy_writer::header (npy_io.hpp), restated so that this header stays free of the HIP runtime.
 #pragma once
@@ -9,6 +10,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -209,6 +211,94 @@ inline void write_files(const std::string& dir, const host_index& h)
   one("hashed_dataset.npy", 'u', 1, {h.n_rows, h.n_sub}, h.codes);
   one("hashed_dataset_soar.npy", 'u', 1, {h.n_rows, h.n_sub}, h.soar_codes);
   if (h.bf16 != nullptr) one("bf16_dataset.npy", 'i', 2, {h.n_rows, h.dim}, h.bf16);
+}
+
+// ---------------------------------------------------------------- search-side lists (scann_search.hip)
+constexpr int kTileEntries      = 32;          // entries of a code tile: one matrix-core operand
+constexpr uint32_t kNoRow       = 0xffffffffu; // row id of a padding entry
+constexpr uint32_t kMaxReorder  = 4096;
+constexpr int64_t kMaxSearchDim = 2048;        // the 32 staged query rows have to fit LDS
+
+inline uint16_t bf16_rne_bits(float f)
+{
+  uint32_t u;
+  std::memcpy(&u, &f, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return (uint16_t)(u >> 16);
+}
+
+inline void check_search(int metric, uint32_t n_probes, uint32_t n_reorder, int64_t k, bool has_bf16, int64_t dim, int64_t query_dim)
+{
+  if (!(metric == 0 || metric == 6)) refuse("ScaNN search serves L2Expanded and InnerProduct, the index records metric %d", metric);
+  if (query_dim != dim) refuse("queries have %lld columns, the index has dim %lld", (long long)query_dim, (long long)dim);
+  if (dim > kMaxSearchDim) refuse("ScaNN search serves up to %lld dimensions, the index has %lld", (long long)kMaxSearchDim, (long long)dim);
+  if (n_probes < 1) refuse("n_probes must be positive");
+  if (k < 1) refuse("k must be positive");
+  if (n_reorder > kMaxReorder) refuse("n_reorder (%u) must not exceed %u", n_reorder, kMaxReorder);
+  if (n_reorder > 0 && !has_bf16) refuse("n_reorder > 0 needs an index built with reordering_bf16 (cuvsRefine re-ranks against the caller's rows)");
+  if (n_reorder > 0 && k > (int64_t)n_reorder) refuse("k (%lld) must not exceed n_reorder (%u)", (long long)k, n_reorder);
+  if (n_reorder == 0 && k > (int64_t)kMaxReorder) refuse("k (%lld) must not exceed %u", (long long)k, kMaxReorder);
+}
+
+// Leaf j: an entry with the primary codes for every row whose label is j and one with the SOAR codes for every row whose SOAR
+// label is j and differs from its label, in ascending row id. A leaf starts at a whole tile of 32 entries; entry p of a leaf is
+// slot (tile_off[j] + p / 32) * 32 + p % 32 of ids and t, and its codes are byte s % 4 of words[(tile * n_words + s / 4) * 32 + p % 32]
+// for subspace s: a tile's lanes read consecutive words. Subspaces past the last one (dimensions up to dim_pad) hold code 0 and
+// meet the zero padding of the codebook rows.
+struct search_lists {
+  int64_t dim_pad = 0, n_words = 0, n_tiles = 0, n_spilled = 0;
+  std::vector<uint32_t> leaf_size, tile_off;  // [n_leaves], [n_leaves + 1]
+  std::vector<uint32_t> ids, words;           // [n_tiles * 32], [n_tiles * n_words * 32]
+  std::vector<float> t;                       // [n_tiles * 32]: 2 <centre, r~> + |r~|^2 (L2; fp64 sums, rounded once), else 0
+  std::vector<uint16_t> book_bf16;            // [book_n, dim_pad], zero-padded
+};
+
+inline search_lists build_search_lists(const host_index& h, bool l2)
+{
+  if (h.n_rows >= (int64_t)kNoRow) refuse("ScaNN search serves fewer than 2^32 - 1 rows");
+  search_lists s;
+  const int64_t W = h.pq_dim;
+  s.dim_pad       = (h.dim + 15) / 16 * 16;
+  s.n_words       = ((s.dim_pad - 1) / W) / 4 + 1;
+  s.leaf_size.assign((size_t)h.n_leaves, 0);
+  for (int64_t i = 0; i < h.n_rows; ++i) {
+    if (h.labels[i] >= h.n_leaves || h.soar[i] >= h.n_leaves) refuse("row %lld has a label outside the %lld leaves", (long long)i, (long long)h.n_leaves);
+    ++s.leaf_size[h.labels[i]];
+    if (h.soar[i] != h.labels[i]) { ++s.leaf_size[h.soar[i]]; ++s.n_spilled; }
+  }
+  s.tile_off.assign((size_t)h.n_leaves + 1, 0);
+  for (int64_t j = 0; j < h.n_leaves; ++j) s.tile_off[j + 1] = s.tile_off[j] + (s.leaf_size[j] + kTileEntries - 1) / kTileEntries;
+  s.n_tiles = s.tile_off[h.n_leaves];
+  s.ids.assign((size_t)s.n_tiles * kTileEntries, kNoRow);
+  s.t.assign((size_t)s.n_tiles * kTileEntries, 0.0f);
+  s.words.assign((size_t)(s.n_tiles * s.n_words) * kTileEntries, 0u);
+  s.book_bf16.assign((size_t)(h.book_n * s.dim_pad), 0);
+  for (int64_t e = 0; e < h.book_n; ++e)
+    for (int64_t d = 0; d < h.dim; ++d) s.book_bf16[e * s.dim_pad + d] = bf16_rne_bits(h.codebook[e * h.dim + d]);
+  std::vector<uint32_t> cursor((size_t)h.n_leaves, 0);
+  auto put = [&](int64_t row, uint32_t leaf, const uint8_t* codes) {
+    const uint32_t p    = cursor[leaf]++;
+    const int64_t tile  = s.tile_off[leaf] + p / kTileEntries;
+    const int64_t lane  = p % kTileEntries;
+    s.ids[tile * kTileEntries + lane] = (uint32_t)row;
+    double cr = 0.0, rr = 0.0;
+    for (int64_t j = 0; j < h.n_sub; ++j) {
+      if (codes[j] >= h.book_n) refuse("row %lld has a code outside the %lld entries of the codebook", (long long)row, (long long)h.book_n);
+      s.words[(tile * s.n_words + j / 4) * kTileEntries + lane] |= (uint32_t)codes[j] << (8 * (j % 4));
+      for (int64_t d = j * W; d < (j + 1) * W; ++d) {
+        const double r = h.codebook[(int64_t)codes[j] * h.dim + d];
+        cr += (double)h.centers[(int64_t)leaf * h.dim + d] * r;
+        rr += r * r;
+      }
+    }
+    if (l2) s.t[tile * kTileEntries + lane] = (float)(2.0 * cr + rr);
+  };
+  for (int64_t i = 0; i < h.n_rows; ++i) {
+    put(i, h.labels[i], h.codes + i * h.n_sub);
+    if (h.soar[i] != h.labels[i]) put(i, h.soar[i], h.soar_codes + i * h.n_sub);
+  }
+  return s;
 }
 
 }  // namespace scann_host

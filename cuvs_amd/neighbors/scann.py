@@ -1,8 +1,9 @@
-"""ScaNN index build (reference: cuvs::neighbors::experimental::scann, cpp/include/cuvs/neighbors/scann.hpp, build-only there;
+"""ScaNN index build and search (reference: cuvs::neighbors::experimental::scann, cpp/include/cuvs/neighbors/scann.hpp, build-only there;
 C entry points: include/cuvs_amd/scann.h; arithmetic and deviations: DESIGN.md 3.1z).
 
 The dataset is a torch tensor on the device, or a numpy array / host tensor that is streamed in batches of 65536 rows (same index
-bit for bit); fp32, row-major. `save` writes the .npy files that open-source ScaNN reads. There is no search here."""
+bit for bit); fp32, row-major. `save` writes the .npy files that open-source ScaNN reads. `search` (include/cuvs_amd/scann_search.h,
+DESIGN.md 3.1za) is an extension: the reference has none."""
 import ctypes as C
 import os
 
@@ -12,6 +13,7 @@ import torch
 from .._lib import DLManagedTensor, Tensor, check, lib, view_to_torch
 from ..common import auto_sync_resources
 from ..distance import DISTANCE_TYPES
+from ._util import as_device, out_buffers
 
 
 class _CParams(C.Structure):
@@ -147,6 +149,51 @@ def save(dirname, index, resources=None):
     """Writes the index files into the directory (created when missing)."""
     os.makedirs(dirname, exist_ok=True)
     check(lib().cuvsAmdScannSerialize(resources.get_c_obj(), os.fsencode(dirname), index._p))
+
+
+class _CSearchParams(C.Structure):
+    _fields_ = [("n_probes", C.c_uint32), ("n_reorder", C.c_uint32)]
+
+
+class SearchParams:
+    """n_probes leaves per query; n_reorder candidates re-ranked against the index's bf16 rows (0: the approximate scores)."""
+
+    def __init__(self, n_probes=20, n_reorder=0):
+        self._p = C.POINTER(_CSearchParams)()
+        check(lib().cuvsAmdScannSearchParamsCreate(C.byref(self._p)))
+        self._p.contents.n_probes = n_probes
+        self._p.contents.n_reorder = n_reorder
+
+    n_probes = property(lambda self: self._p.contents.n_probes)
+    n_reorder = property(lambda self: self._p.contents.n_reorder)
+
+    def __del__(self):
+        try:
+            if self._p:
+                lib().cuvsAmdScannSearchParamsDestroy(self._p)
+        except Exception:
+            pass
+
+
+@auto_sync_resources
+def search(search_params, index, queries, k, resources=None):
+    """queries fp32 [m, dim] -> (distances fp32 [m, k], neighbors int64 [m, k]) on the device, by the metric recorded in the index
+    (sqeuclidean ascending, inner_product descending)"""
+    if not index.trained:
+        raise ValueError("Index needs to be built before calling search.")
+    q = as_device(queries)
+    neighbors, distances = out_buffers(q.shape[0], k, None, None)
+    tq, tn, td = Tensor(q), Tensor(neighbors), Tensor(distances)
+    check(lib().cuvsAmdScannSearch(resources.get_c_obj(), search_params._p, index._p, tq.ptr, tn.ptr, td.ptr))
+    return distances, neighbors
+
+
+def search_last_stats():
+    """The calling thread's last search: units scanned, (entry, query) pairs scored, units that read the codebook from global
+    memory, candidates dropped as duplicates."""
+    out = (C.c_uint64 * 4)()
+    check(lib().cuvsAmdScannSearchLastStats(out))
+    return list(out)
 
 
 def _u32(t):

@@ -12,6 +12,7 @@
 #include <cuvs_amd/extensions.h>
 #include <cuvs_amd/ivf_rabitq.h>
 #include <cuvs_amd/scann.h>
+#include <cuvs_amd/scann_search.h>
 #include <cuvs_amd/sparse.h>
 
 #include <array>
@@ -728,7 +729,7 @@ inline std::array<uint64_t, 4> last_stats()
 
 namespace experimental {
 namespace scann {
-// scann.hpp: build-only. Partitions by balanced k-means, AVQ centres, SOAR labels, PQ codes of both residuals, optional bf16 rows,
+// scann.hpp (build-only there; search is this library's extension). Partitions by balanced k-means, AVQ centres, SOAR labels, PQ codes of both residuals, optional bf16 rows,
 // and the files open-source ScaNN reads (include/cuvs_amd/scann.h). pq_dim is the width of a subspace.
 struct index_params {
   cuvsDistanceType metric     = L2Expanded;
@@ -829,6 +830,28 @@ inline void quantize_bf16(const resources& res, device_matrix_view<const float> 
   detail::tensor<const float> d(dataset);
   detail::tensor<int16_t> o(out);
   check(cuvsAmdScannQuantizeBf16(res.get(), d.get(), threshold, o.get()), "cuvsAmdScannQuantizeBf16");
+}
+// search (include/cuvs_amd/scann_search.h): n_reorder candidates are re-ranked against the index's bf16 rows
+// (0: the approximate scores); neighbors int64 [m, k] and distances fp32 [m, k] on the device
+struct search_params {
+  uint32_t n_probes  = 20;
+  uint32_t n_reorder = 0;
+};
+inline void search(const resources& res, const search_params& p, const index& idx, device_matrix_view<const float> queries,
+                   device_matrix_view<int64_t> neighbors, device_matrix_view<float> distances)
+{
+  cuvsAmdScannSearchParams cp{p.n_probes, p.n_reorder};
+  detail::tensor<const float> q(queries);
+  detail::tensor<int64_t> n(neighbors);
+  detail::tensor<float> d(distances);
+  check(cuvsAmdScannSearch(res.get(), &cp, idx.get(), q.get(), n.get(), d.get()), "cuvsAmdScannSearch");
+}
+// the calling thread's last search: units scanned, (entry, query) pairs scored, units without the codebook in LDS, duplicates dropped
+inline std::array<uint64_t, 4> search_last_stats()
+{
+  std::array<uint64_t, 4> out{};
+  check(cuvsAmdScannSearchLastStats(out.data()), "cuvsAmdScannSearchLastStats");
+  return out;
 }
 }  // namespace scann
 }  // namespace experimental

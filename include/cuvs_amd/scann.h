@@ -5,7 +5,8 @@
  * DESIGN.md 3.1z has the arithmetic, the deviations from what the reference executes and the kernels.
  *
  * Rows are fp32, row-major and contiguous, on the device or on the host (host rows are streamed in batches of at most 65536
- * and give the same index bit for bit). Finite inputs are the caller's responsibility. There is no search and no reader.
+ * and give the same index bit for bit). Finite inputs are the caller's responsibility. The search is in scann_search.h; there is
+ * no reader of the files.
  */
 #pragma once
 #include <cuvs/core/c_api.h>
