@@ -64,3 +64,4 @@ def pairwise_distance(X, Y, out=None, metric="euclidean", p=2.0, resources=None)
 
 
 from ._sparse import SPARSE_DISTANCES, set_sparse_walk_form, sparse_last_stats, sparse_pairwise_distance, validate_csr  # noqa: E402,F401
+from ._masked import cross_component_nn, masked_l2_nn, masked_nn_last_stats  # noqa: E402,F401
