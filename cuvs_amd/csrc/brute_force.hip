@@ -155,6 +155,56 @@ __global__ void bf_emit_topk_kernel(const float* __restrict__ buf_v, const int64
   out_i[t] = buf_i[row * ldb + j];
 }
 
+}  // namespace
+
+void bf_tile_shape(resources& res, int64_t m, int64_t n, int k, int64_t* m_tile, int64_t* n_tile)
+{
+  const int64_t ws_floats = (int64_t)(res.workspace_limit / sizeof(float));
+  *m_tile                 = std::min<int64_t>(m, k > 2048 ? 256 : 16384);
+  *n_tile                 = std::max<int64_t>(128, (ws_floats / *m_tile) / 128 * 128);
+  *n_tile                 = std::min<int64_t>(*n_tile, round_up(n, 128));
+}
+
+// ---- the per-tile select path: a distance tile per (row tile, column tile) from `tile_fn`, the pre-filter applied to it,
+// select_k per tile and one merging select_k over the column tiles' partial results. Row tiles whose `redo` flag is clear are
+// left as they are; `guard` (optional, one device word per row tile) makes every launch of a row tile a no-op while its
+// word is zero. bf_search_typed runs it over pairwise_distance; binary_knn.hip over its Hamming tiles.
+void bf_select_tiles(resources& res, int64_t m, int64_t n, int k, bool select_min, int64_t m_tile, int64_t n_tile, float* tile,
+                     int64_t ldo, const std::vector<char>& redo, const int* guard, const uint32_t* filter_bits, int filter_type,
+                     float* part_v, int64_t* part_i, const bf_tile_fn& tile_fn, int64_t* neighbors, float* distances)
+{
+  const int64_t n_ct = (n + n_tile - 1) / n_tile;
+  const float worst  = select_min ? FLT_MAX : -FLT_MAX;
+  for (int64_t r0 = 0; r0 < m; r0 += m_tile) {
+    if (!redo[(size_t)(r0 / m_tile)]) continue;
+    const int64_t mr = std::min(m_tile, m - r0);
+    const uint32_t* run_if = guard != nullptr ? reinterpret_cast<const uint32_t*>(guard + r0 / m_tile) : nullptr;
+    for (int64_t ct = 0; ct < n_ct; ++ct) {
+      const int64_t c0 = ct * n_tile;
+      const int64_t nc = std::min(n_tile, n - c0);
+      tile_fn(r0, mr, c0, nc, tile, ldo, run_if);
+      if (filter_type != NO_FILTER) {
+        int64_t total = mr * nc;
+        hipLaunchKernelGGL(apply_filter_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 1 << 22)), dim3(256), 0, res.stream,
+                           tile, mr, nc, ldo, c0, r0, n, filter_bits, filter_type == BITMAP, worst, run_if);
+      }
+      if (n_ct == 1) {
+        select_k<int64_t, int64_t>(res, tile, nullptr, mr, nc, ldo, k, distances + r0 * k,
+                                   neighbors + r0 * k, select_min, c0, -1, 0, run_if);
+      } else {
+        select_k<int64_t, int64_t>(res, tile, nullptr, mr, nc, ldo, k, part_v, part_i,
+                                   select_min, c0, n_ct * k, ct * k, run_if);
+      }
+    }
+    if (n_ct > 1) {
+      select_k<int64_t, int64_t>(res, part_v, part_i, mr, n_ct * k, n_ct * k, k,
+                                 distances + r0 * k, neighbors + r0 * k, select_min, 0, -1, 0, run_if);
+    }
+  }
+}
+
+namespace {
+
 template <typename T>
 void bf_search_typed(resources& res, const bf_index& idx, const T* queries, int64_t m, int64_t ldq, int k,
                      int64_t* neighbors, float* distances, const uint32_t* filter_bits, int filter_type)
@@ -169,11 +219,9 @@ void bf_search_typed(resources& res, const bf_index& idx, const T* queries, int6
 
   // row tiles bounded by the workspace; column tiles as wide as the workspace allows. Large k (beyond the 2048
   // winners select_k keeps in LDS at full speed) shrinks the row tile so that the per-tile partial results stay small.
-  const int64_t ws_floats = (int64_t)(res.workspace_limit / sizeof(float));
-  int64_t m_tile          = std::min<int64_t>(m, k > 2048 ? 256 : 16384);
-  int64_t n_tile          = std::max<int64_t>(128, (ws_floats / m_tile) / 128 * 128);
-  n_tile                  = std::min<int64_t>(n_tile, round_up(n, 128));
-  const int64_t n_ct      = (n + n_tile - 1) / n_tile;
+  int64_t m_tile = 0, n_tile = 0;
+  bf_tile_shape(res, m, n, k, &m_tile, &n_tile);
+  const int64_t n_ct = (n + n_tile - 1) / n_tile;
 
   dev_buf<float> qn;
   if (metric != M_InnerProduct) {
@@ -339,34 +387,14 @@ void bf_search_typed(resources& res, const bf_index& idx, const T* queries, int6
     part_i = dev_buf<int64_t>(res, (size_t)m_tile * n_ct * k);
   }
 
-  for (int64_t r0 = 0; r0 < m; r0 += m_tile) {
-    if (!redo[(size_t)(r0 / m_tile)]) continue;
-    const int64_t mr = std::min(m_tile, m - r0);
-    const uint32_t* run_if = guarded ? reinterpret_cast<const uint32_t*>(ovf.data() + r0 / m_tile) : nullptr;
-    for (int64_t ct = 0; ct < n_ct; ++ct) {
-      const int64_t c0 = ct * n_tile;
-      const int64_t nc = std::min(n_tile, n - c0);
-      pairwise_distance<T, T>(res, queries + r0 * ldq, mr, ldq, data + c0 * idx.ld, nc, idx.ld, idx.dim,
-                              qn.data() ? qn.data() + r0 : nullptr,
-                              idx.norms.data() ? idx.norms.data() + c0 : nullptr, metric, tile.data(), ldo, run_if);
-      if (filter_type != NO_FILTER) {
-        int64_t total = mr * nc;
-        hipLaunchKernelGGL(apply_filter_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 1 << 22)), dim3(256), 0, res.stream,
-                           tile.data(), mr, nc, ldo, c0, r0, n, filter_bits, filter_type == BITMAP, worst, run_if);
-      }
-      if (n_ct == 1) {
-        select_k<int64_t, int64_t>(res, tile.data(), nullptr, mr, nc, ldo, k, distances + r0 * k,
-                                   neighbors + r0 * k, select_min, c0, -1, 0, run_if);
-      } else {
-        select_k<int64_t, int64_t>(res, tile.data(), nullptr, mr, nc, ldo, k, part_v.data(), part_i.data(),
-                                   select_min, c0, n_ct * k, ct * k, run_if);
-      }
-    }
-    if (n_ct > 1) {
-      select_k<int64_t, int64_t>(res, part_v.data(), part_i.data(), mr, n_ct * k, n_ct * k, k,
-                                 distances + r0 * k, neighbors + r0 * k, select_min, 0, -1, 0, run_if);
-    }
-  }
+  bf_select_tiles(res, m, n, k, select_min, m_tile, n_tile, tile.data(), ldo, redo, guarded ? ovf.data() : nullptr, filter_bits, filter_type,
+                  part_v.data(), part_i.data(),
+                  [&](int64_t r0, int64_t mr, int64_t c0, int64_t nc, float* out, int64_t ld, const uint32_t* run_if) {
+                    pairwise_distance<T, T>(res, queries + r0 * ldq, mr, ldq, data + c0 * idx.ld, nc, idx.ld, idx.dim,
+                                            qn.data() ? qn.data() + r0 : nullptr, idx.norms.data() ? idx.norms.data() + c0 : nullptr,
+                                            metric, out, ld, run_if);
+                  },
+                  neighbors, distances);
   HIP_TRY(hipGetLastError());
 }
 

@@ -3,6 +3,8 @@
 #pragma once
 #include "common.hpp"
 
+#include <functional>
+
 namespace cuvs_amd {
 
 // ---------------------------------------------------------------- select_k.hip
@@ -166,6 +168,17 @@ void refine(resources& res, const void* data, elem_t et, int64_t n, int64_t dim,
 // cuvsBruteForceSearch: missing slots hold the worst value and id -1, filtered rows the worst value.
 void bf_search_view(resources& res, int metric, const float* data, int64_t n, int64_t dim, const float* norms,
                     const float* queries, int64_t m, int k, int64_t* neighbors, float* distances, const uint32_t* bits);
+// The tiled search's machinery over distance tiles somebody else computes (binary_knn.hip). bf_tile_shape: the row / column
+// tile of an m x n search at this k under the handle's workspace limit. bf_select_tiles: for every row tile whose `redo` flag
+// is set and every column tile, tile_fn writes the fp32 tile [mr, nc] (pitch ld) of rows r0.. x columns c0..; the BITSET /
+// BITMAP pre-filter (cuvsBruteForceSearch's conventions) is applied to it, select_k takes its top k and one more select_k
+// merges the column tiles (part_v / part_i [m_tile, n_ct * k], needed for more than one column tile). guard: nullptr, or
+// one device word per row tile that turns the row tile's launches into no-ops while it is zero.
+using bf_tile_fn = std::function<void(int64_t r0, int64_t mr, int64_t c0, int64_t nc, float* tile, int64_t ld, const uint32_t* run_if)>;
+void bf_tile_shape(resources& res, int64_t m, int64_t n, int k, int64_t* m_tile, int64_t* n_tile);
+void bf_select_tiles(resources& res, int64_t m, int64_t n, int k, bool select_min, int64_t m_tile, int64_t n_tile, float* tile,
+                     int64_t ldo, const std::vector<char>& redo, const int* guard, const uint32_t* filter_bits, int filter_type,
+                     float* part_v, int64_t* part_i, const bf_tile_fn& tile_fn, int64_t* neighbors, float* distances);
 
 // ---------------------------------------------------------------- mg.hip helpers (defined next to the index structs)
 void ivf_flat_index_info(uintptr_t addr, int64_t* size, int* metric);
